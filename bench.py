@@ -1,10 +1,21 @@
 """Benchmark of the ARCO 2-D hot-path training step on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N > 1 without a torchrun environment: this process spawns `python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N ...` (one rank per GPU over RCCL) BEFORE touching the GPU and relays rank 0's JSON line; under
 torchrun (WORLD_SIZE set) it is one rank.  A world size different from --gpus is an error (exit code 2).
 Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).
+--dump-outputs DIR: after the timed steps (and after --full's measurements), the timed path - the same trainer, graphs and
+arguments - takes its last step once more, untimed, on the last timed step's batch but from a state that is the same in
+every run: the seeded initial weights, full banks of seeded keys, reseeded generators (dropout's included).  Rank 0 writes
+what that step produced as DIR/<name>.npy (float32): the returned loss and loss terms, the student's parameters and buffers
+and the EMA teacher's parameters (a fixed, seeded sample of any array above DUMP_MAX_ELEMS elements).  Two runs with the
+same arguments agree to rounding.  (The state the timed steps start from cannot serve: fp32 atomics in the backward of the
+heads and of the anchor gradient leave ~1e-7 relative differences in every step's gradient, and a chain of training steps
+amplifies them - after a few hundred steps two runs' weights and sampled anchors differ outright.)
+--full: everything else below, measured after the timed region as well.
 
 Workload = BASELINE.json configs[1]: ACDC-shaped 2-D 256x256, --batch_size 8 per stream (16 images/step/GPU), C=4,
 D=496, stratified sampler (smc) + 4096-key/class queue, nq=256, nn=512, temp 0.5; synthetic data and random-init weights
@@ -13,10 +24,11 @@ a step = SURVEY §8a rows N1-N5, T1, L1-L6, O1 plus the §8f row-1 terms the ref
 unsupervised CE, the TPS equivariance term with its extra student pass) and the cutmix mixing of --apply_aug.
 Weak scaling: per-GPU work is fixed; value = N*K 16-image steps / wall time (max over ranks).
 
-The timed region runs the product configuration with NO instrumentation.  Afterwards, outside the timed region:
-a sustained run (>= --sustain_s seconds), a k2 = 0 run (the north-star path alone), an eager pass with HIP events
-around the conv / weight-gradient launches for the roofline objects (graphs off: the kernels must be visible to the
-events), sub-records for BASELINE.json configs[2..4] (each in a child process) and the CPU baseline.
+The timed region runs the product configuration with NO instrumentation.  With --full, afterwards, outside the timed
+region: the contrastive-loss segments on HIP events, a sustained run (>= --sustain_s seconds), a k2 = 0 run (the north-star
+path alone), an eager pass with HIP events around the conv / weight-gradient launches for the roofline objects (graphs
+off: the kernels must be visible to the events), sub-records for BASELINE.json configs[2..4] (each in a child process)
+and the CPU baseline.
 """
 import argparse
 import json
@@ -403,6 +415,77 @@ def step_roofline(work, step_ms, split=True):
                     "frac_of_lower_bound is the whole-step roofline fraction"}
 
 
+DUMP_MAX_ELEMS = 1 << 22          # per array: 16 MB of float32; the whole dump stays under 64 MB
+
+
+def step_outputs(stepper, ret):
+    """What the last step handed its caller, as host arrays: the returned loss and reconstruction loss, the loss terms,
+    the student's parameters (the optimiser's flat buffer: U-Net, q_representation, FeatureExtractor) and float buffers
+    (BatchNorm statistics), and the EMA teacher's parameters."""
+    import numpy as np
+    loss, reco = ret
+    out = {"loss": loss.reshape(1), "reco_loss": reco.reshape(1)}
+    for k, v in stepper.last_terms.items():
+        out["term_" + k] = torch.as_tensor(v).reshape(1)
+    out["student_params"] = stepper.optimizer.flat_p
+    bufs = [b.reshape(-1) for b in stepper.model.buffers() if b.is_floating_point()]
+    if bufs:
+        out["student_buffers"] = torch.cat(bufs)
+    out["teacher_params"] = torch.cat([p.detach().reshape(-1) for p in
+                                       list(stepper.ema_model.parameters()) + list(stepper.k_feature_extractor.parameters())])
+    arrays = {}
+    for k, v in out.items():
+        a = v.detach().float().cpu().numpy().reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:           # a fixed, seeded sample of the larger arrays (same positions in every run)
+            a = a[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        arrays[k] = a.astype(np.float32)
+    return arrays
+
+
+def _trainer_modules(st):
+    return (st.isd, st.k_feature_extractor, st.q_feature_extractor, st.q_representation)     # isd: student, EMA teacher, its queues
+
+
+def trainer_snapshot(st):
+    """The seeded initial weights of an ArcoStep2D: student (the optimiser's flat buffers), EMA teacher, key encoder, lr schedule."""
+    return dict(p=st.optimizer.flat_p.clone(), b=st.optimizer.flat_buf.clone(), started=list(st.optimizer._started),
+                lr=[g['lr'] for g in st.optimizer.param_groups], it=st.iter_num,
+                sd=[{k: v.clone() for k, v in m.state_dict().items()} for m in _trainer_modules(st)])
+
+
+def trainer_reset(st, snap, seed):
+    """Back to `snap`'s weights with every class bank FULL of seeded keys (as the warm-up leaves them: queue_size keys each) and
+    the generators reseeded: the steps that follow start from the same state in every run, whatever earlier steps' fp32
+    atomics left behind."""
+    import random
+    import numpy as np
+    from arco_amd import ops
+    with torch.no_grad():
+        st.optimizer.flat_p.copy_(snap["p"])
+        st.optimizer.flat_buf.copy_(snap["b"])
+        st.optimizer._started = list(snap["started"])
+        for g, lr in zip(st.optimizer.param_groups, snap["lr"]):
+            g['lr'] = lr
+        for m, sd in zip(_trainer_modules(st), snap["sd"]):
+            for k, v in m.state_dict().items():
+                v.copy_(sd[k])
+        gen = torch.Generator().manual_seed(seed)
+        for c, q in enumerate(st.memobank):
+            q[0] = torch.randn(int(st.queue_size[c]), int(q[0].shape[1]), generator=gen).to(q[0].device)
+            st.queue_ptrlis[c][0] = int(st.queue_size[c])
+    st.iter_num = snap["it"]
+    ops.bump_weight_epoch()
+    random.seed(seed); np.random.seed(seed); torch.manual_seed(seed)
+    ops.reseed_dropout(seed)
+
+
+def dump_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def timed(run_steps, n):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -564,7 +647,14 @@ def main():
     ap.add_argument("--batch_transform", type=int, default=1, help="the reference's batch_transform (PIL round trip, jitter, blur, AdvMorph); 0: off")
     ap.add_argument("--conv_mma", type=str, default="f32x3", help="matrix-core mode: f32x3 (default, split-bf16, fp32-accurate) or f32 (native fp32 MFMA)")
     ap.add_argument("--head_levels", type=int, default=-1, help="row-sparse head depth of the trainer (default: the trainer's)")
-    ap.add_argument("--settle_s", type=float, default=2.5, help="untimed steps for this many seconds before the warmup (clock settling)")
+    ap.add_argument("--settle_steps", type=int, default=240,
+                    help="untimed steps before the warmup (clock settling: >= 2.5 s of load at ~10.5 ms per step); a fixed count, so "
+                         "that the timed steps start from the same state in every run")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", type=str, default="",
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: contrastive-loss segments, sustained and k2 = 0 runs, roofline, "
+                         "configs[2..4] / forced-dist / drop-in-user sub-records, CPU baseline")
     ap.add_argument("--cpu_baseline_child", action="store_true")
     ap.add_argument("--sub", type=str, default="")
     ap.add_argument("--sub_steps", type=int, default=6)
@@ -601,6 +691,7 @@ def main():
     stepper = T.ArcoStep2D(args, dev)
     if world > 1:             # per-rank generator streams (cutmix boxes, sampler indices, TPS warps), after the weight broadcast
         adist.seed_data_pipeline(1337)
+    init_state = trainer_snapshot(stepper) if a.dump_outputs else None
     b = a.batch_size
     batches = []
     for i in range(4):        # a few resident synthetic batches, cycled
@@ -608,24 +699,24 @@ def main():
         u_img, _ = T.synthetic_batch(b, args.patch_size, args.num_classes, 101 + 2 * i * world + rank, dev)
         batches.append((l_img, l_lab, u_img))
     cursor = [0]
+    last = [None]
 
     def run(n):
         for _ in range(n):
             l_img, l_lab, u_img = batches[cursor[0] % len(batches)]
             cursor[0] += 1
-            stepper.step(l_img, l_lab, u_img, 0, 100)
+            last[0] = stepper.step(l_img, l_lab, u_img, 0, 100)
 
     # one-off costs - HIP-graph capture on a pass's third call, first use of the 50 %-probability augmentation branches
     # (AdvMorph, blur), pinned staging buffers, allocator growth - must lie before the timed region whatever --warmup is:
     # extra untimed steps only (measured: isolated 60-90 ms steps as late as step 11, tools/step_times.py)
     run(max(0, 14 - a.warmup))
     # ... and so must the power-management transient: on these boxes the step runs at 16.4 ms for the first ~0.7 s of load,
-    # 18-19 ms for the next ~0.7 s, and settles at the sustained rate from ~1.6 s on (tools/step_times.py, N=500:
-    # gpurun_out/steptimes_r2h.log).  Untimed steps until the device has been busy for a_settle seconds, so the
-    # K timed steps measure the settled clocks whatever K and W are.
-    t_pre = time.perf_counter()
-    while a.settle_s > 0 and time.perf_counter() - t_pre < a.settle_s:
-        run(10)
+    # 18-19 ms for the next ~0.7 s, and settles at the sustained rate from ~1.6 s on (tools/step_times.py, N=500).
+    # --settle_steps untimed steps (>= 2.5 s of load at the settled rate), so the K timed steps measure the settled clocks whatever
+    # K and W are.  A step count rather than a time: every run with the same arguments takes the same steps.
+    for i in range(0, max(0, a.settle_steps), 10):
+        run(min(10, a.settle_steps - i))
         torch.cuda.synchronize()
     run(a.warmup)
     if world > 1:
@@ -638,28 +729,31 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # contrastive-loss ms/step (the metric's second half): HIP events around the three loss segments, in a separate pass
-    # after the timed region.  The student passes run eagerly in this pass: an event recorded right behind a HIP-graph
-    # replay is timestamped unreliably on this stack (the kernel trace of the same step shows the segment's kernels back to
-    # back: profiles/README.md), so the graph-replayed passes next to the segments are launched as plain kernels here.
-    from arco_amd import graphs as _graphs
-    # (the instrumented passes below run on ONE stream: HIP events on the launch stream cannot price a segment or a kernel while
-    #  another pass runs beside it on the side stream - T.TEACHER_SIDE is the step's pass-concurrency switch)
-    side_mode, T.TEACHER_SIDE = T.TEACHER_SIDE, 0
-    prev_flags = _graphs.set_enabled(stepper, {"s_train_tps": False, "s_train_lu": False})
-    stepper.profile_loss = True
-    stepper.loss_events = []
-    run(8)
-    torch.cuda.synchronize()
-    evs = stepper.loss_events[2:]
-    loss_seg = [round(sum(e[i][0].elapsed_time(e[i][1]) for e in evs) / max(1, len(evs)), 3) for i in range(3)]
-    if evs and len(evs[0]) > 3 and evs[0][3] is not None:       # row lists + prototypes: queued ahead of the host sync since round 2
-        loss_seg[1] = round(loss_seg[1] + sum(e[3][0].elapsed_time(e[3][1]) for e in evs) / len(evs), 3)
-    loss_ms = sum(loss_seg)
-    stepper.profile_loss = False
-    stepper.loss_events = []
-    _graphs.set_enabled(stepper, prev_flags)
-    T.TEACHER_SIDE = side_mode
+    last_timed_batch = (cursor[0] - 1) % len(batches)
+    side_mode = T.TEACHER_SIDE
+    if a.full:
+        # contrastive-loss ms/step (the metric's second half): HIP events around the three loss segments, in a separate pass
+        # after the timed region.  The student passes run eagerly in this pass: an event recorded right behind a HIP-graph
+        # replay is timestamped unreliably on this stack (the kernel trace of the same step shows the segment's kernels back to
+        # back: profiles/README.md), so the graph-replayed passes next to the segments are launched as plain kernels here.
+        from arco_amd import graphs as _graphs
+        # (the instrumented passes below run on ONE stream: HIP events on the launch stream cannot price a segment or a kernel while
+        #  another pass runs beside it on the side stream - T.TEACHER_SIDE is the step's pass-concurrency switch)
+        T.TEACHER_SIDE = 0
+        prev_flags = _graphs.set_enabled(stepper, {"s_train_tps": False, "s_train_lu": False})
+        stepper.profile_loss = True
+        stepper.loss_events = []
+        run(8)
+        torch.cuda.synchronize()
+        evs = stepper.loss_events[2:]
+        loss_seg = [round(sum(e[i][0].elapsed_time(e[i][1]) for e in evs) / max(1, len(evs)), 3) for i in range(3)]
+        if evs and len(evs[0]) > 3 and evs[0][3] is not None:       # row lists + prototypes: queued ahead of the host sync since round 2
+            loss_seg[1] = round(loss_seg[1] + sum(e[3][0].elapsed_time(e[3][1]) for e in evs) / len(evs), 3)
+        loss_ms = sum(loss_seg)
+        stepper.profile_loss = False
+        stepper.loss_events = []
+        _graphs.set_enabled(stepper, prev_flags)
+        T.TEACHER_SIDE = side_mode
     ranks_seen = 1
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -671,7 +765,7 @@ def main():
     step_ms = dt / a.steps * 1e3
 
     sustained = k2_0 = roof = whole = step_roof = None
-    if world == 1:
+    if a.full and world == 1:
         if a.sustain_s > 0:              # clocks settle lower under sustained load: a >= 3 s figure beside the K-step one
             n_s = max(a.steps, int(a.sustain_s * 1e3 / step_ms) + 1)
             ms_s = timed(run, n_s)
@@ -685,13 +779,26 @@ def main():
             k2_0 = {"ms_per_step": round(ms0, 3), "steps_per_s": round(1e3 / ms0, 3), "steps": a.k2_0_steps,
                     "note": "--k2 0: the north-star path alone (contrastive + supervised + unsupervised terms), no "
                             "equivariance pass; round 1's headline configuration"}
-    # the roofline objects at every N: each rank runs the same instrumented eager steps (they contain the step's collectives, so
-    # all ranks take part); rank 0's launches are the ones reported
-    T.TEACHER_SIDE = 0            # single-stream eager pass: per-kernel HIP-event timing (see above)
-    prof = eager_profile(stepper, run, 3)
-    T.TEACHER_SIDE = side_mode
-    roof, whole = roofline_from_profile(prof, 3, step_ms)
-    step_roof = step_roofline(prof.get("__work__"), step_ms, split=a.conv_mma == "f32x3")
+    if a.full:
+        # the roofline objects at every N: each rank runs the same instrumented eager steps (they contain the step's collectives, so
+        # all ranks take part); rank 0's launches are the ones reported
+        T.TEACHER_SIDE = 0            # single-stream eager pass: per-kernel HIP-event timing (see above)
+        prof = eager_profile(stepper, run, 3)
+        T.TEACHER_SIDE = side_mode
+        roof, whole = roofline_from_profile(prof, 3, step_ms)
+        step_roof = step_roofline(prof.get("__work__"), step_ms, split=a.conv_mma == "f32x3")
+    if a.dump_outputs:
+        # the timed path's last step once more, on its batch, from the same state in every run (see the module docstring);
+        # every rank takes part
+        trainer_reset(stepper, init_state, 1337)
+        if world > 1:
+            adist.seed_data_pipeline(1337)
+        cursor[0] = last_timed_batch
+        run(1)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, step_outputs(stepper, last[0]))
+        del init_state
 
     if rank == 0:
         out = {
@@ -699,42 +806,48 @@ def main():
             "unit": "steps/s (16-image steps, all GPUs)", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(step_ms, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            # the short scalars first (a truncated copy of this line keeps them): contrastive-loss ms/step is the metric's other half
-            "contrastive_loss_ms_per_step": round(loss_ms, 3),
-            "sustained_ms_per_step": (sustained or {}).get("ms_per_step"),
-            "sustained_steps_per_s": (sustained or {}).get("steps_per_s"),
-            "whole_step_tflops": (whole or {}).get("tflops_over_whole_step"),
-            "k2_0_ms_per_step": (k2_0 or {}).get("ms_per_step"),
-            "config": {"workload": f"ACDC 2D 256x256 bs=16 per GPU on {world}xMI355X, stratified sampler + 4096-key/class queue "
-                                   "(BASELINE.json configs[1]), reference-default flags",
-                       "batch_size_per_stream": b, "images_per_step_per_gpu": 2 * b,
-                       "classes": 4, "rep_dim": 496, "num_queries": 256, "num_negatives": 512, "func": "smc", "apply_aug": args.apply_aug,
-                       "loss_terms": f"k1*contrastive + k3*unsupervised + CE + Dice + k2*equivariance (k2 = {a.k2:g})",
-                       "graph_train": int(bool(getattr(args, "graph_train", 0))), "parallelism": f"dp{world}",
-                       "pass_concurrency": f"ARCO_TEACHER_SIDE={T.TEACHER_SIDE} (teacher / statistics / warped student passes on a second stream), ARCO_SIDE_SYNC={T.SIDE_SYNC} (round 4's host-side wait in front of backward; 0 = off since the round-5 kernel fix)",
-                       "contrastive_loss_ms_per_step": round(loss_ms, 3),
-                       "sustained_ms_per_step": (sustained or {}).get("ms_per_step"),
-                       "whole_step_tflops": (whole or {}).get("tflops_over_whole_step")},
-            # compute_contra_memobank_loss on the GPU clock: masks | lists, prototypes, keys, banks | anchors, row-sparse head,
-            # InfoNCE INCLUDING its analytic gradient w.r.t. the anchors (the loss's backward is computed in the forward)
-            "contrastive_loss_segments_ms": {"masks_counts": loss_seg[0], "lists_prototypes_keys_banks": loss_seg[1],
-                                             "anchors_head_infonce": loss_seg[2]},
-            "roofline": roof,
-            "step_roofline": step_roof,
-            "ranks_seen": ranks_seen,
         }
+        config = {"workload": f"ACDC 2D 256x256 bs=16 per GPU on {world}xMI355X, stratified sampler + 4096-key/class queue "
+                              "(BASELINE.json configs[1]), reference-default flags",
+                  "batch_size_per_stream": b, "images_per_step_per_gpu": 2 * b,
+                  "classes": 4, "rep_dim": 496, "num_queries": 256, "num_negatives": 512, "func": "smc", "apply_aug": args.apply_aug,
+                  "loss_terms": f"k1*contrastive + k3*unsupervised + CE + Dice + k2*equivariance (k2 = {a.k2:g})",
+                  "graph_train": int(bool(getattr(args, "graph_train", 0))), "parallelism": f"dp{world}",
+                  "pass_concurrency": f"ARCO_TEACHER_SIDE={T.TEACHER_SIDE} (teacher / statistics / warped student passes on a second stream), ARCO_SIDE_SYNC={T.SIDE_SYNC} (round 4's host-side wait in front of backward; 0 = off since the round-5 kernel fix)"}
+        if a.full:
+            out.update({
+                # the short scalars first (a truncated copy of this line keeps them): contrastive-loss ms/step is the metric's other half
+                "contrastive_loss_ms_per_step": round(loss_ms, 3),
+                "sustained_ms_per_step": (sustained or {}).get("ms_per_step"),
+                "sustained_steps_per_s": (sustained or {}).get("steps_per_s"),
+                "whole_step_tflops": (whole or {}).get("tflops_over_whole_step"),
+                "k2_0_ms_per_step": (k2_0 or {}).get("ms_per_step")})
+            config.update({"contrastive_loss_ms_per_step": round(loss_ms, 3),
+                           "sustained_ms_per_step": (sustained or {}).get("ms_per_step"),
+                           "whole_step_tflops": (whole or {}).get("tflops_over_whole_step")})
+        out["config"] = config
+        if a.full:
+            out.update({
+                # compute_contra_memobank_loss on the GPU clock: masks | lists, prototypes, keys, banks | anchors, row-sparse head,
+                # InfoNCE INCLUDING its analytic gradient w.r.t. the anchors (the loss's backward is computed in the forward)
+                "contrastive_loss_segments_ms": {"masks_counts": loss_seg[0], "lists_prototypes_keys_banks": loss_seg[1],
+                                                 "anchors_head_infonce": loss_seg[2]},
+                "roofline": roof,
+                "step_roofline": step_roof})
+        out["ranks_seen"] = ranks_seen
         if whole is not None:
             out["whole_step"] = whole
         if sustained is not None:
             out["sustained"] = sustained
         if k2_0 is not None:
             out["north_star_path_only_k2_0"] = k2_0
-        if world == 1 and not a.no_subs:
+        if a.full and world == 1 and not a.no_subs:
             del stepper
             batches.clear()
+            last.clear()
             torch.cuda.empty_cache()
             out["configs"] = [sub_record(n, a.sub_steps) for n in SUBS] + [forced_dist_record(), dropin_user_record()]
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if world > 1:

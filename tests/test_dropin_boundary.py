@@ -83,58 +83,6 @@ def test_surface_covers_the_names_the_verdict_named():
     assert {"np", "nn", "F"} <= set(t2["loss_helper_3d"])                 # aliases the trainer never imports itself
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/code"), reason="the reference tree exists in the build container only")
-@pytest.mark.parametrize("trainer", ["train_arco_2d.py", "train_arco_3d.py", "pretrain_2D.py", "pretrain_3D.py"])
-def test_reference_trainer_import_block_runs_against_dropin(trainer):
-    """Build container only: the REAL import block of the reference trainer (every top-level import statement of the file,
-    in order, third-party packages absent from this image stubbed) executed with PYTHONPATH = dropin : code, then every
-    name the trainer's code loads is looked up in the resulting namespace - what `python train_arco_2d.py` does up to
-    its first statement."""
-    child = r'''
-import ast, builtins, sys, types
-trainer, dropin, code = sys.argv[1:4]
-sys.path[:0] = [dropin, code]
-class _Stub(types.ModuleType):
-    def __getattr__(self, n):
-        if n.startswith("__"):
-            raise AttributeError(n)
-        return _Stub(self.__name__ + "." + n)
-    def __call__(self, *a, **k):
-        return None
-for name in ("tensorboardX", "torchvision", "torchvision.transforms", "torchvision.utils", "torchvision.models", "h5py", "medpy",
-             "SimpleITK", "nibabel", "skimage", "skimage.measure"):
-    try:
-        __import__(name)
-    except Exception:
-        sys.modules[name] = _Stub(name)
-src = open(code + "/" + trainer).read()
-tree = ast.parse(src)
-ns = {"__name__": "trainer_imports"}
-for node in tree.body:
-    if isinstance(node, (ast.Import, ast.ImportFrom)):
-        exec(compile(ast.Module([node], []), trainer, "exec"), ns)
-bound = set()
-for n in ast.walk(tree):
-    if isinstance(n, ast.Name) and not isinstance(n.ctx, ast.Load): bound.add(n.id)
-    elif isinstance(n, (ast.FunctionDef, ast.ClassDef)): bound.add(n.name)
-    elif isinstance(n, ast.arg): bound.add(n.arg)
-loads = {n.id for n in ast.walk(tree) if isinstance(n, ast.Name) and isinstance(n.ctx, ast.Load)}
-missing = sorted(n for n in loads if n not in ns and n not in bound and not hasattr(builtins, n))
-from_ref = sorted(k for k, m in sys.modules.items() if getattr(m, "__file__", None) and m.__file__.startswith(code)
-                  and not k.startswith(("networks.", "utils.util", "dataloaders.utils", "tps_stn")))
-print("MISSING", missing)
-print("FROM_REF", from_ref)
-'''
-    r = subprocess.run([sys.executable, "-c", child, trainer, os.path.join(ROOT, "dropin"), "/root/reference/code"],
-                       capture_output=True, text=True, cwd="/", env=dict(os.environ, PYTHONPATH=""), timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = dict(l.split(" ", 1) for l in r.stdout.strip().splitlines() if l.startswith(("MISSING", "FROM_REF")))
-    assert out["MISSING"] == "[]", out
-    # hot-path modules must come from dropin/, not from the reference tree (dataloaders.utils, which the stage-1 trainers
-    # import and never use, is allowed to fall through to the reference's own file: namespace packages merge)
-    assert out["FROM_REF"] == "[]", out
-
-
 _SHADOW_CHILD = r'''
 import sys
 sys.path.insert(0, sys.argv[1])

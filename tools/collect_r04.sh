@@ -1,7 +1,7 @@
 #!/bin/bash
 # on the GPU box: the round's evidence in one call -> gpurun_out/r04h_*  (copied into profiles/ afterwards)
 root=$(pwd); export TMPDIR=/tmp; o=$root/gpurun_out
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $o/r04h_bench.json 2> $o/r04h_bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $o/r04h_bench.json 2> $o/r04h_bench.err
 bash tools/prof_run.sh r04h 40 > $o/r04h_prof2d.txt 2>&1
 bash tools/prof_run3d.sh r04h > $o/r04h_prof3d.txt 2>&1
 bash tools/prof_run3d.sh r04h_lits "SHAPE=1 160 160 96" ACT_DTYPE=f16 > $o/r04h_prof3d_lits.txt 2>&1

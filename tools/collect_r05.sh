@@ -1,7 +1,7 @@
 #!/bin/bash
 # on the GPU box: the round's evidence in one call -> gpurun_out/r05_*  (copied into profiles/ afterwards)
 root=$(pwd); export TMPDIR=/tmp; o=$root/gpurun_out
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $o/r05_bench.json 2> $o/r05_bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $o/r05_bench.json 2> $o/r05_bench.err
 bash tools/prof_run.sh r05 40 > $o/r05_prof2d.txt 2>&1
 bash tools/prof_run3d.sh r05 > $o/r05_prof3d.txt 2>&1
 bash tools/prof_run3d.sh r05_lits "SHAPE=1 160 160 96" ACT_DTYPE=f16 > $o/r05_prof3d_lits.txt 2>&1

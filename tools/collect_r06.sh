@@ -1,7 +1,7 @@
 #!/bin/bash
 # on the GPU box: the round's evidence in one call -> gpurun_out/r06_*  (copied into profiles/ afterwards)
 root=$(pwd); export TMPDIR=/tmp; o=$root/gpurun_out
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $o/r06_bench.json 2> $o/r06_bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $o/r06_bench.json 2> $o/r06_bench.err
 bash tools/prof_run.sh r06 40 > $o/r06_prof2d.txt 2>&1
 bash tools/prof_run3d.sh r06 > $o/r06_prof3d.txt 2>&1
 bash tools/prof_run3d.sh r06_lits "SHAPE=1 160 160 96" ACT_DTYPE=f16 > $o/r06_prof3d_lits.txt 2>&1

@@ -3,7 +3,7 @@ root=$(pwd); o=$root/gpurun_out; export TMPDIR=/tmp
 python -m pytest tests/test_loss_gpu.py tests/test_dropin_user_gpu.py -x -q 2>&1 | tail -25 > $o/r06_c5_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" >> $o/r06_c5_tests.log 2>&1
 for rep in 1 2; do for v in 0 1; do
-  ARCO_NCE_FUSED=$v python3 bench.py --gpus 1 --steps 20 --warmup 5 --no_subs --no_cpu_baseline 2>/dev/null | tail -1 > $o/ab_nce_${v}_${rep}.json
+  ARCO_NCE_FUSED=$v python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no_subs --no_cpu_baseline 2>/dev/null | tail -1 > $o/ab_nce_${v}_${rep}.json
 done; done
 python3 - <<'P' >> $o/r06_c5_tests.log
 import json, glob
