@@ -81,6 +81,13 @@ _SIGS = {
     "arco_d2s3_add_h": [_P, _L, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P],
     "arco_cast_h2f": [_P, _L, _P, _P],
     "arco_cast_f2h": [_P, _L, _F, _P, _P],
+    "arco_conv3x3_image_fwd_h": [_P, _L, _I, _P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P],
+    "arco_conv3x3_image_wgrad_h": [_P, _L, _I, _P, _L, _I, _I, _I, _I, _P, _P, _I, _P],
+    "arco_maxpool2_fwd_h": [_P, _L, _I, _I, _I, _I, _P, _L, _P],
+    "arco_maxpool2_bwd_h": [_P, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
+    "arco_maxpool2_bwd_add_h": [_P, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P],
+    "arco_bilinear_fwd_h": [_P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P],
+    "arco_bilinear_bwd_h": [_P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P],
     "arco_gn_finalize": [_P, _P, _I, _I, _I, _I, _L, _F, _P, _P, _P],
     "arco_gn_act_bwd": [_P, _L, _P, _L, _L, _I, _P, _P, _P, _P, _F, _P, _P, _P, _I, _P, _L, _I, _I, _P],
     "arco_maxpool2_fwd": [_P, _L, _I, _I, _I, _I, _P, _L, _P],
@@ -147,6 +154,7 @@ _QUERIES = {   # plain host helpers returning sizes
     "arco_jitter_desc_bytes": ([], _L),
     "arco_conv_mblocks": ([_I, _I, _I, _I, _I, _I, _L, _I], _I),
     "arco_conv_mblocks_mma": ([_I, _I, _I, _I, _I, _I, _L, _I, _I], _I),
+    "arco_conv3x3_image_mblocks_h": ([_I, _I, _I, _I], _I),
     "arco_conv_mblocks_pro": ([_I, _I, _I, _I, _I, _I, _L, _I, _I, _I], _I),
     "arco_conv_config": ([_I, _I, _I, _I, _I, _I, _L, _P], _I),
     "arco_conv_config_mma": ([_I, _I, _I, _I, _I, _I, _L, _I], _I),

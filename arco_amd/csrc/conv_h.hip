@@ -9,6 +9,8 @@
 //                    fp32 accumulate, D = W . X^T so that a lane ends with 4 consecutive channels of one pixel (8-byte
 //                    stores); BatchNorm partial statistics of the ROUNDED outputs in the epilogue.  Double-buffered LDS:
 //                    chunk c+1 is loaded to registers and written to the other buffer around the MFMAs of chunk c.
+//                    DEPTH = 1: the same plane step without the depth loop - the 3x3 convolutions of the 2-D path (U-Net, --act_dtype f16
+//                    of train_arco_2d; hconv_dispatch2); rows that are not whole 16-byte pieces are staged element-wise there.
 //   hwgrad_kernel    weight gradient dW[tap][co][ci] = sum_pix dZ[pix][co] X[pix + tap][ci] (K = pixels).  Both operands
 //                    sit in LDS exactly as they sit in HBM ([pixel][channel] rows) and are read through
 //                    ds_read_b64_tr_b16 - the transposing LDS read of gfx950 hands every lane 4 consecutive PIXELS of one
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(256) void hconv_kernel(IgemmArgs a) {
 #pragma unroll
     for (int it = 0; it < NA; ++it) {
       u32x4 v = u32x4{0, 0, 0, 0};
-      if (TAPS == 1 && !vecA) {        // rows that are not whole 16-byte pieces (the 2-class logits' gradient: K = 2)
+      if ((TAPS == 1 || DEPTH == 1) && !vecA) {        // rows that are not whole 16-byte pieces (the 2-class logits' gradient: K = 2; the U-Net's out_conv gradient: K = 4 / 19)
         if (srcA[it]) {
           h8 e8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -980,8 +982,30 @@ static int hconv1x1_stream_dispatch(const IgemmArgs& a, hipStream_t st) {
 }
 
 // entry of the f16-storage convolutions (called from arco_conv3d_fwd with mma == 4).  a.Kpad = ceil32(K) (the f16 pack)
+// 3x3 on 2-D maps (the U-Net): hconv_kernel's plane step without the depth loop (DEPTH = 1), rectangular tiles of BM / 16 rows x 16
+// columns (ragged at the edges).  Tile choice as hconv_dispatch3's: the largest tile that still gives `want` workgroups.
+static int hconv_dispatch2(const IgemmArgs& a, hipStream_t st, int* q) {
+  static const long want = getenv("ARCO_HCONV2_WANT") ? atol(getenv("ARCO_HCONV2_WANT")) : 256;
+  auto blocks = [&](int bm, int bn) { return h_rect_blocks(a, bm, bn); };
+  if (a.Npad <= 16) return blocks(128, 16) >= want ? launch_hconv<9, 128, 16, 4, 1, 1, false>(a, st, q) : launch_hconv<9, 64, 16, 4, 1, 1, false>(a, st, q);
+  if (a.Npad <= 32) {
+    if (blocks(256, 32) >= want) return launch_hconv<9, 256, 32, 4, 1, 1, false>(a, st, q);
+    if (blocks(128, 32) >= want) return launch_hconv<9, 128, 32, 4, 1, 1, false>(a, st, q);
+    return launch_hconv<9, 64, 32, 2, 2, 1, false>(a, st, q);
+  }
+  if (blocks(128, 64) >= want) return launch_hconv<9, 128, 64, 4, 1, 1, false>(a, st, q);
+  if (blocks(64, 64) >= want) return launch_hconv<9, 64, 64, 2, 2, 1, false>(a, st, q);
+  if (blocks(64, 32) >= want) return launch_hconv<9, 64, 32, 2, 2, 1, false>(a, st, q);
+  return launch_hconv<9, 32, 32, 2, 2, 1, false>(a, st, q);
+}
+
 int hconv_dispatch(const IgemmArgs& a, int taps, hipStream_t st, int* q) {
-  if ((taps != 1 && ((a.K & 7) != 0 || (a.lda & 7) != 0)) || a.R != nullptr) return ARCO_ERR_UNSUPPORTED;
+  if ((taps == 27 && ((a.K & 7) != 0 || (a.lda & 7) != 0)) || a.R != nullptr) return ARCO_ERR_UNSUPPORTED;
+  if (taps == 9) {        // (rows that are not whole 16-byte pieces - the gradient of a narrow out_conv - are staged element-wise)
+    if (!q && (reinterpret_cast<uintptr_t>(a.Wp) & 15) != 0) return ARCO_ERR_ARG;
+    if (!q && (a.K & 7) == 0 && (a.lda & 7) == 0 && (reinterpret_cast<uintptr_t>(a.A) & 15) != 0) return ARCO_ERR_ARG;
+    return hconv_dispatch2(a, st, q);
+  }
   if (!q && (((reinterpret_cast<uintptr_t>(a.A) & 15) != 0 && (a.K & 7) == 0) || (reinterpret_cast<uintptr_t>(a.Wp) & 15) != 0)) return ARCO_ERR_ARG;
   if (taps == 27) {
     if (hconv_rw_eligible(a)) {
@@ -1183,7 +1207,8 @@ int hwgrad_dispatch(const void* dZ, long ld_dz, int Cout, const void* in, long l
   a.dZ = reinterpret_cast<const _Float16*>(dZ); a.ldz = ld_dz; a.Cout = Cout;
   a.X = reinterpret_cast<const _Float16*>(in); a.ldx = ld_in; a.Cin = Cin;
   a.taps = taps; a.NB = NB; a.H = H; a.W = W; a.D3 = D3; a.M = (long)NB * H * W; a.partial = ws;
-  if ((Cin & 7) != 0 || (ld_in & 7) != 0 || (ld_dz & 1) != 0) return ARCO_ERR_UNSUPPORTED;
+  // (2-D 3x3: dZ rows of any width are staged element-wise when they are not whole 16-byte pieces - the U-Net's 19-class out_conv)
+  if ((Cin & 7) != 0 || (ld_in & 7) != 0 || ((ld_dz & 1) != 0 && taps != 9)) return ARCO_ERR_UNSUPPORTED;
   long chunks;
   if (taps >= 9) {
     const int hco = Cout > 16 ? 32 : 16, hci = Cin > 16 ? 32 : 16;

@@ -8,6 +8,12 @@ initialisation and checkpoints are identical); the forward pass never calls them
 it runs the hand-written HIP kernels of arco_amd.ops on channels-last activations:
 conv3x3 (fp32 MFMA implicit GEMM, BN partial statistics fused in the epilogue) ->
 BN finalize -> one fused BN-apply + LeakyReLU + dropout pass.
+
+With ops.ACT_HALF (train_arco_2d --act_dtype f16) a TRAINING-mode forward keeps every activation and activation gradient of the
+network as f16 (csrc/conv_h.hip, csrc/unet_h.hip, the *_h entry points): the first layer reads the fp32 image and writes f16, the
+logits and the feature maps leave as fp32 (ops.from_half, whose backward applies the loss scale).  The two stages of a ConvBlock
+and the pooling run as separate passes there (no consumer-side activation / pooled apply kernel in f16).  Evaluation-mode
+forwards stay on the fp32 route whatever ops.ACT_HALF says.
 """
 import torch
 import torch.nn as nn
@@ -136,6 +142,10 @@ class Encoder(nn.Module):
 
     def forward(self, x):
         x = ops.to_channels_last(x.to(torch.float32))
+        with ops.open_half(self.training and ops.ACT_HALF):      # f16 activation storage: in_conv's first layer opens the region
+            return self._forward(x)
+
+    def _forward(self, x):
         if self.training and ops.POOL_FUSE:     # nn.MaxPool2d of each DownBlock fused into the block before it; the two
             x0, p = self.in_conv(x, pool=True)  # gradients of x_i (skip + pooling) are summed in that block's backward
             x1, p = self.down1.maxpool_conv[1](p, pool=True)
@@ -184,7 +194,10 @@ class Decoder(nn.Module):
         x = self.up4(x, x0)
         feature_map.append(x)
         output = ops.conv(x, self.out_conv.weight, self.out_conv.bias)
-        return output, feature_map
+        # f16 activation storage (ops.ACT_HALF, training mode): the logits and the feature maps leave the f16 region as fp32 - heads,
+        # losses and samplers are fp32; gradients come back through the same boundary with the loss scale
+        # (inside `with ops.logits_only():` the maps are handed out as stored, as the V-Net's are)
+        return ops.from_half(output), ([ops.from_half(f) for f in feature_map] if ops.FM_CAST else feature_map)
 
 
 class UNet(nn.Module):
@@ -219,4 +232,7 @@ class UNet(nn.Module):
     def forward(self, x):
         feature = self.encoder(x)
         output, feature_map = self.decoder(feature)
-        return output, feature[-1], feature_map
+        x4 = feature[-1]
+        if x4.dtype == torch.float16 and ops.FM_CAST:      # f16 activation storage: the bottleneck map leaves as fp32, cast once
+            x4 = feature_map[0]
+        return output, x4, feature_map

@@ -296,7 +296,7 @@ class PackPlan:
                 n, k = (co, ci) if mode == 0 else (ci, co)
                 npad, kpad = _ceil16(n), _ceil16(k)
                 buf = sbuf = hbuf = None
-                if m_half and isinstance(m, torch.nn.Conv3d) and k % 8 == 0 and taps in (1, 27):   # f16 pack (csrc/conv_h.hip)
+                if m_half and k % 8 == 0 and (taps in (1, 27) if isinstance(m, torch.nn.Conv3d) else taps in (1, 9) and ci > 4):   # f16 pack (csrc/conv_h.hip)
                     kp32 = (k + 31) // 32 * 32
                     hbuf = torch.empty((taps, npad, kp32), dtype=torch.float16, device=dev)
                     recs.append((w, hbuf, co, ci, taps, mode | 4, npad, kp32, total))
@@ -453,10 +453,37 @@ def pack_weight(weight, taps, mode, half=False):
     return wp
 
 
+_OPEN_HALF_2D = False
+
+
+class open_half:
+    """`with ops.open_half(on):` - a 3x3 convolution of an fp32 IMAGE (<= 4 channels) inside writes f16: the U-Net's first layer
+    opens the f16 region (unetWithArgs.Encoder enters it in training mode only; evaluation stays on the fp32 route)."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        global _OPEN_HALF_2D
+        self.prev, _OPEN_HALF_2D = _OPEN_HALF_2D, self.on
+
+    def __exit__(self, *exc):
+        global _OPEN_HALF_2D
+        _OPEN_HALF_2D = self.prev
+
+
 def use_half(x, taps, ci):
     """Does a convolution of x run on the f16-storage kernels?  Yes when x is f16, or when x is the fp32 one-channel volume
-    entering the V-Net's first 3x3x3 layer in f16 mode (that layer's output opens the f16 region)."""
-    return _is_half(x) or (ACT_HALF and taps == 27 and ci == 1 and x.dim() == 5)
+    entering the V-Net's first 3x3x3 layer in f16 mode (that layer's output opens the f16 region), or the fp32 image entering
+    the U-Net's first 3x3 layer inside `ops.open_half()`."""
+    return _is_half(x) or (ACT_HALF and taps == 27 and ci == 1 and x.dim() == 5) \
+        or (_OPEN_HALF_2D and taps == 9 and ci <= 4 and x.dim() == 4)
+
+
+def _half_pack(half, taps, ci):
+    """Does an f16-storage convolution read the f16 weight pack?  Not the layers that open the region: they read an fp32 input
+    (the V-Net's one-channel volume, the U-Net's image of <= 4 channels) with the fp32 pack."""
+    return bool(half) and not (ci == 1 or (taps == 9 and ci <= 4))
 
 
 def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=0, stats=False, d3=1, sp=None,
@@ -477,14 +504,20 @@ def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=
     elif d3 > 1:
         out = new_act_nd(nb, n, (d3, h, w), xr.device, odt)
     else:
-        out = new_act(nb, n, h, w, xr.device)
+        out = new_act_nd(nb, n, (h, w), xr.device, odt)
     if outr is None:
         outr, ld_out = out, n
     mma = 0
+    image_h = False         # the U-Net's first layer in f16 mode: fp32 image in, f16 out (csrc/unet_h.hip)
     if half:
-        if residual is not None or (d3 <= 1 and sp is None):
-            raise RuntimeError("arco_amd: f16 activation storage covers the volume path's convolutions without a residual operand")
+        if residual is not None:
+            raise RuntimeError("arco_amd: f16 activation storage covers convolutions without a residual operand")
+        if pro is not None:
+            raise RuntimeError("arco_amd: f16 activation storage has no consumer-side activation (ops.conv_block returns None)")
         mma = 4
+        image_h = taps == 9 and d3 == 1 and not _is_half(xr)
+        if image_h and (k > 4 or n > 16 or n % 4):
+            raise RuntimeError(f"arco_amd: f16 activation storage opens at a 3x3 layer of <= 4 -> 16 channels, got {k} -> {n}")
     elif HEAD_MMA and taps == 1 and pro is None:
         mma = 2 if grad else HEAD_MMA                     # (wp is the fp32 pack: the operands are rounded in registers)
     elif CONV_MMA == 3:
@@ -496,7 +529,9 @@ def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=
     ssum = ssq = None
     nmb = 0
     if stats:
-        if pro is not None and taps == 27:       # the 3x3x3 forms with the activation in their loaders tile differently
+        if image_h:
+            nmb = L.query("arco_conv3x3_image_mblocks_h", nb, h, w, stat_groups)
+        elif pro is not None and taps == 27:       # the 3x3x3 forms with the activation in their loaders tile differently
             nmb = L.query("arco_conv_mblocks_pro", taps, nb * d3, h, w, k, n, ld, stat_groups, mma, pro_groups)
         else:
             nmb = L.query("arco_conv_mblocks_mma", taps, nb * d3, h, w, k, n, ld, stat_groups, mma)
@@ -507,7 +542,7 @@ def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=
         mpix = nb * d3 * h * w
         _work(mpix * (k + n) * esz + taps * n * k * 4 + (mpix * n * esz if residual is not None else 0), 2.0 * taps * mpix * n * k)
     prof = cfg = None
-    if PROFILE is not None and not torch.cuda.is_current_stream_capturing():
+    if PROFILE is not None and not image_h and not torch.cuda.is_current_stream_capturing():
         # every launch is counted; every PROFILE_EVERY-th one is bracketed by HIP events on the launch stream
         # (an event pair per launch costs ~1.5 ms/step of stream bubbles at ~350 conv launches per step)
         key = (taps, nb * d3, h, w, k, n, ld, mma)
@@ -522,7 +557,10 @@ def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=
         if rec["n"] % PROFILE_EVERY == 1 % PROFILE_EVERY:
             prof = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             prof[0].record()
-    if pro is not None:
+    if image_h:
+        L.call("arco_conv3x3_image_fwd_h", L.ptr(xr), ld, k, L.ptr(wp), n, L.ptr(outr), ld_out, L.ptr(bias), L.ptr(ssum), L.ptr(ssq),
+               nb, h, w, stat_groups if stats else 1)
+    elif pro is not None:
         if mma != 3:
             raise RuntimeError("arco_amd: a consumer-side activation needs the split-bf16 kernels (ops.pro_ok)")
         L.call("arco_conv3d_fwd_pro", L.ptr(xr), ld, k, L.ptr(wp), n, L.ptr(outr), ld_out, L.ptr(bias), L.ptr(residual), ld_res,
@@ -557,7 +595,10 @@ def conv_wgrad(dzr, ldz, co, xr, ldx, ci, taps, nb, h, w, like, d3=1, pro=None):
             mma = 4
         else:
             mma = 3 if (CONV_MMA == 3 and taps in (9, 27)) else (2 if (CONV_MMA in (1, 2) and taps == 27) else 0)
-        if pro is not None:
+        if mma == 4 and taps == 9 and d3 == 1 and ci > 1 and not _is_half(xr):      # the U-Net's first layer on a 2- to 4-channel image:
+            # fp32 image x f16 gradient (a one-channel image takes the matrix-core kernel the V-Net's first layer uses, below: 38 vs 161 us)
+            L.call("arco_conv3x3_image_wgrad_h", L.ptr(dzr), ldz, co, L.ptr(xr), ldx, ci, nb, h, w, L.ptr(ws), L.ptr(out), accumulate)
+        elif pro is not None:
             L.call("arco_conv3d_wgrad_pro", L.ptr(dzr), ldz, co, L.ptr(xr), ldx, ci, taps, nb, d3, h, w, L.ptr(ws), L.ptr(out),
                    accumulate, mma, pro)
         else:
@@ -744,7 +785,7 @@ class ConvFn(torch.autograd.Function):
         xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
         co = int(weight.shape[0])
         half = use_half(x, taps, ci)
-        wp = pack_weight(weight, taps, 0, half=half and ci != 1)
+        wp = pack_weight(weight, taps, 0, half=_half_pack(half, taps, ci))
         if isinstance(residual, torch.Tensor):              # y = conv(x) + R  (R: any tensor of y's shape)
             rr, ldr = rows_view(residual)
             res_self = False
@@ -842,7 +883,7 @@ class ConvBnActFn(torch.autograd.Function):
         co = int(weight.shape[0])
         m = nv * d3 * h * w
         half = use_half(x, taps, ci)
-        wp = pack_weight(weight, taps, 0, half=half and ci != 1)
+        wp = pack_weight(weight, taps, 0, half=_half_pack(half, taps, ci))
         G = BN_GROUPS
         if G > 1 and nv % G != 0:
             raise RuntimeError(f"arco_amd: bn_groups({G}) needs a batch that is a multiple of {G}, got {nv}")
@@ -851,7 +892,7 @@ class ConvBnActFn(torch.autograd.Function):
         mean, istd = _finalize_bn(ssum, ssq, nmb, co, m, eps, momentum, running_mean, running_var, nbt, G, x.device)
         seed = _next_seed() if p > 0 else 0
         if cat_room:        # leave room behind the channels for a later in-place channel concat (ops.upcat)
-            buf = new_act_nd(nv, co + int(cat_room), sp, x.device)
+            buf = new_act_nd(nv, co + int(cat_room), sp, x.device, z.dtype)
             a, ld_a = buf[:, :co], co + int(cat_room)
             _LAST_CAT_BUF = buf
         else:
@@ -864,10 +905,15 @@ class ConvBnActFn(torch.autograd.Function):
         if pool:            # the activation AND its 2x2 max-pool in one pass (encoder blocks: next DownBlock + decoder skip)
             if p > 0 or d3 != 1:
                 raise RuntimeError("arco_amd: conv_bn_act(pool=True) is the 2-D, dropout-free last stage of a ConvBlock")
-            pooled = new_act(nv, co, h // 2, w // 2, x.device)
-            _work((2 * m + m // 4) * co * 4)
-            L.call("arco_bn_act_pool_fwd", L.ptr(zr), ldz, nv, h, w, co, L.ptr(mean), L.ptr(istd), L.ptr(gamma), L.ptr(beta),
-                   float(slope), L.ptr(a), ld_a, L.ptr(pooled), co, G)
+            pooled = new_act_nd(nv, co, (h // 2, w // 2), x.device, z.dtype)
+            if _is_half(zr):      # f16 storage: the apply pass and the pooling pass run separately (no pooled apply kernel in f16)
+                _bn_apply(zr, ldz, m, co, mean, istd, gamma, beta, slope, drop_mode, 0.0, 0, h * w, a, ld_a, G)
+                _work((m + m // 4) * co * 2)
+                L.call("arco_maxpool2_fwd_h", L.ptr(a), ld_a, nv, h, w, co, L.ptr(pooled), co)
+            else:
+                _work((2 * m + m // 4) * co * 4)
+                L.call("arco_bn_act_pool_fwd", L.ptr(zr), ldz, nv, h, w, co, L.ptr(mean), L.ptr(istd), L.ptr(gamma), L.ptr(beta),
+                       float(slope), L.ptr(a), ld_a, L.ptr(pooled), co, G)
             ctx.seed_dev = None
             ctx.set_materialize_grads(False)
             ctx.save_for_backward(x, weight, z, mean, istd, gamma, beta, a)
@@ -888,15 +934,7 @@ class ConvBnActFn(torch.autograd.Function):
         co = int(weight.shape[0])
         if ctx.pool and dpool is not None:       # d a = d skip + maxpool2_bwd(d pooled), summed inside the pooling backward
             ar, lda_ = rows_view(a)
-            dpr, ldp = rows_view(dpool)
-            dsum = new_act(nv, co, h, w, x.device)
-            _work((nv * h * w * (3 if da is not None else 2) + nv * h * w // 4) * co * 4)
-            if da is None:
-                L.call("arco_maxpool2_bwd", L.ptr(ar), lda_, nv, h, w, co, L.ptr(dpr), ldp, L.ptr(dsum), co)
-            else:
-                sr, lds = rows_view(da)
-                L.call("arco_maxpool2_bwd_add", L.ptr(ar), lda_, nv, h, w, co, L.ptr(dpr), ldp, L.ptr(sr), lds, L.ptr(dsum), co)
-            da = dsum
+            da = _maxpool2_backward(ar, lda_, nv, h, w, co, dpool, da)
         dz, dgamma, dbeta = _bn_backward(da, z, mean, istd, gamma, beta, slope, drop_mode, p, seed, d3 * h * w,
                                          ctx.seed_dev, ctx.groups)
         dzr, ldzz = rows_view(dz)
@@ -1114,8 +1152,8 @@ def conv_block(x, conv1, bn1, act1, p1, conv2, bn2, act2, cat_room=0, pool=False
     """The train-mode ConvBlock: ConvBlockFn when both convolutions run on the pipelined kernels (ops.pro_ok), else None (the
     caller runs the two stages separately)."""
     global _LAST_CAT_BUF
-    if not BLOCK_FUSE or x.dim() != 4 or x.dtype != torch.float32:
-        return None
+    if not BLOCK_FUSE or x.dim() != 4 or x.dtype != torch.float32 or use_half(x, 9, int(x.shape[1])):
+        return None       # (f16 activation storage runs the two stages separately: no consumer-side activation in the f16 loaders)
     xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
     cm, co = int(conv1.weight.shape[0]), int(conv2.weight.shape[0])
     if _taps(conv1.weight) != 9 or _taps(conv2.weight) != 9 or not pro_ok(9, nv, 1, h, w, cm, co, cm, BN_GROUPS):
@@ -1350,14 +1388,40 @@ class TrilinearFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+def _maxpool2_forward(x):
+    """maxpool2 of a channels-last activation; follows x's storage type (fp32 / f16)."""
+    xr, ld, nb, c, h, w = _geom(x)
+    y = new_act_nd(nb, c, (h // 2, w // 2), x.device, xr.dtype)
+    L.call("arco_maxpool2_fwd_h" if _is_half(xr) else "arco_maxpool2_fwd", L.ptr(xr), ld, nb, h, w, c, L.ptr(y), c)
+    return y
+
+
+def _maxpool2_backward(xr, ld, nb, h, w, c, dy, dskip):
+    """maxpool2_bwd(dy) (+ dskip, the gradient of x's other consumer, inside the same kernel); follows x's storage type."""
+    half = _is_half(xr)
+    if _is_half(dy) != half:           # a gradient that reached an f16 activation in fp32 (or the reverse): follow the activation
+        dy = dy.to(xr.dtype)
+    if dskip is not None and _is_half(dskip) != half:
+        dskip = dskip.to(xr.dtype)
+    dyr, ldy = rows_view(dy)
+    dx = new_act_nd(nb, c, (h, w), xr.device, xr.dtype)
+    esz = 2 if half else 4
+    _work((nb * h * w * (3 if dskip is not None else 2) + nb * h * w // 4) * c * esz)
+    if dskip is None:
+        L.call("arco_maxpool2_bwd_h" if half else "arco_maxpool2_bwd", L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy, L.ptr(dx), c)
+    else:
+        sr, lds = rows_view(dskip)
+        L.call("arco_maxpool2_bwd_add_h" if half else "arco_maxpool2_bwd_add", L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy,
+               L.ptr(sr), lds, L.ptr(dx), c)
+    return dx
+
+
 class MaxPool2Fn(torch.autograd.Function):
     """nn.MaxPool2d(2) (unetWithArgs.py:55-58)."""
 
     @staticmethod
     def forward(ctx, x):
-        xr, ld, nb, c, h, w = _geom(x)
-        y = new_act(nb, c, h // 2, w // 2, x.device)
-        L.call("arco_maxpool2_fwd", L.ptr(xr), ld, nb, h, w, c, L.ptr(y), c)
+        y = _maxpool2_forward(x)
         ctx.save_for_backward(x)
         return y
 
@@ -1365,10 +1429,7 @@ class MaxPool2Fn(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         xr, ld, nb, c, h, w = _geom(x)
-        dyr, ldy = rows_view(dy)
-        dx = new_act(nb, c, h, w, x.device)
-        L.call("arco_maxpool2_bwd", L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy, L.ptr(dx), c)
-        return dx
+        return _maxpool2_backward(xr, ld, nb, h, w, c, dy, None)
 
 
 class MaxPoolSkipFn(torch.autograd.Function):
@@ -1378,9 +1439,7 @@ class MaxPoolSkipFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        xr, ld, nb, c, h, w = _geom(x)
-        y = new_act(nb, c, h // 2, w // 2, x.device)
-        L.call("arco_maxpool2_fwd", L.ptr(xr), ld, nb, h, w, c, L.ptr(y), c)
+        y = _maxpool2_forward(x)
         ctx.save_for_backward(x)
         return y, x.view_as(x)
 
@@ -1390,14 +1449,25 @@ class MaxPoolSkipFn(torch.autograd.Function):
         xr, ld, nb, c, h, w = _geom(x)
         if dy is None:
             return dskip
-        dyr, ldy = rows_view(dy)
-        dx = new_act(nb, c, h, w, x.device)
-        if dskip is None:
-            L.call("arco_maxpool2_bwd", L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy, L.ptr(dx), c)
-        else:
-            sr, lds = rows_view(dskip)
-            L.call("arco_maxpool2_bwd_add", L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy, L.ptr(sr), lds, L.ptr(dx), c)
-        return dx
+        return _maxpool2_backward(xr, ld, nb, h, w, c, dy, dskip)
+
+
+def _bilinear_forward(xr, ld, nb, h, w, c, ho, wo, out, ld_out):
+    """align_corners bilinear resize of rows xr into `out` (a channels-last tensor or channel slice); follows xr's storage type."""
+    half = _is_half(xr)
+    _work(nb * c * (h * w + ho * wo) * (2 if half else 4))
+    L.call("arco_bilinear_fwd_h" if half else "arco_bilinear_fwd", L.ptr(xr), ld, nb, h, w, c, ho, wo, L.ptr(out), ld_out)
+
+
+def _bilinear_backward(dyr, ldy, nb, h, w, c, ho, wo):
+    half = _is_half(dyr)
+    dx = new_act_nd(nb, c, (h, w), dyr.device, dyr.dtype)
+    _work(nb * c * (h * w + ho * wo) * (2 if half else 4))
+    if half:
+        L.call("arco_bilinear_bwd_h", L.ptr(dyr), ldy, nb, h, w, c, ho, wo, L.ptr(dx), c)
+    else:
+        L.call("arco_bilinear_bwd", L.ptr(dyr), ldy, nb, h, w, c, ho, wo, L.ptr(dx), c, 0)
+    return dx
 
 
 class BilinearFn(torch.autograd.Function):
@@ -1406,20 +1476,18 @@ class BilinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ho, wo):
         xr, ld, nb, c, h, w = _geom(x)
-        y = new_act(nb, c, ho, wo, x.device)
-        _work(nb * c * (h * w + ho * wo) * 4)
-        L.call("arco_bilinear_fwd", L.ptr(xr), ld, nb, h, w, c, ho, wo, L.ptr(y), c)
-        ctx.dims = (nb, c, h, w, ho, wo)
+        y = new_act_nd(nb, c, (ho, wo), x.device, xr.dtype)
+        _bilinear_forward(xr, ld, nb, h, w, c, ho, wo, y, c)
+        ctx.dims = (nb, c, h, w, ho, wo, xr.dtype)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        nb, c, h, w, ho, wo = ctx.dims
+        nb, c, h, w, ho, wo, dt = ctx.dims
+        if dy.dtype != dt:
+            dy = dy.to(dt)
         dyr, ldy = rows_view(dy)
-        dx = new_act(nb, c, h, w, dy.device)
-        _work(nb * c * (h * w + ho * wo) * 4)
-        L.call("arco_bilinear_bwd", L.ptr(dyr), ldy, nb, h, w, c, ho, wo, L.ptr(dx), c, 0)
-        return dx, None, None
+        return _bilinear_backward(dyr, ldy, nb, h, w, c, ho, wo), None, None
 
 
 class _GemmWeightFn(torch.autograd.Function):
@@ -1569,8 +1637,7 @@ class UpCatFn(torch.autograd.Function):
         xr, ld, nb, c, h, w = _geom(x)
         c2, ho, wo = int(skip.shape[1]), int(skip.shape[2]), int(skip.shape[3])
         ctot = int(buf.shape[1])
-        _work(nb * c * (h * w + ho * wo) * 4)
-        L.call("arco_bilinear_fwd", L.ptr(xr), ld, nb, h, w, c, ho, wo, L.ptr(buf[:, c2:]), ctot)
+        _bilinear_forward(xr, ld, nb, h, w, c, ho, wo, buf[:, c2:], ctot)
         ctx.dims = (nb, c, h, w, ho, wo, c2)
         return buf
 
@@ -1578,9 +1645,7 @@ class UpCatFn(torch.autograd.Function):
     def backward(ctx, dbuf):
         nb, c, h, w, ho, wo, c2 = ctx.dims
         dr, ldd = rows_view(dbuf)
-        dx = new_act(nb, c, h, w, dbuf.device)
-        _work(nb * c * (h * w + ho * wo) * 4)
-        L.call("arco_bilinear_bwd", L.ptr(dr[:, c2:]), ldd, nb, h, w, c, ho, wo, L.ptr(dx), c, 0)
+        dx = _bilinear_backward(dr[:, c2:], ldd, nb, h, w, c, ho, wo)
         return dx, dbuf[:, :c2], None
 
 
@@ -1588,7 +1653,7 @@ def upcat(x, skip):
     """cat([skip, bilinear(x, skip.shape[-2:])], 1); in place when `skip` came with concat room."""
     buf = getattr(skip, "_arco_cat_buf", None)
     if (buf is None or buf.shape[1] != skip.shape[1] + x.shape[1] or buf.data_ptr() != skip.data_ptr()
-            or buf.shape[0] != x.shape[0]):
+            or buf.shape[0] != x.shape[0] or buf.dtype != x.dtype):
         return torch.cat([skip, bilinear(x, skip.shape[-2:])], dim=1)
     return UpCatFn.apply(x, skip, buf)
 
@@ -1600,7 +1665,7 @@ def conv_bn_act_eval(x, weight, bias, gamma, beta, running_mean, running_var, sl
         xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
         co = int(weight.shape[0])
         half = use_half(x, taps, ci)
-        z, _ = conv_raw(xr, ld, ci, pack_weight(weight, taps, 0, half=half and ci != 1), co, nv, h, w, taps, bias=bias, d3=d3, sp=sp,
+        z, _ = conv_raw(xr, ld, ci, pack_weight(weight, taps, 0, half=_half_pack(half, taps, ci)), co, nv, h, w, taps, bias=bias, d3=d3, sp=sp,
                         half=half)
         return bn_act_eval(z, gamma, beta, running_mean, running_var, slope, eps)
 

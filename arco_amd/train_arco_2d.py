@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import dist as adist
+from .loss_scale import LossScaleGuard
 from . import _contrast as C_
 from . import augment, glue, graphs, head, ops, optim
 from .tps import RandTPS
@@ -114,6 +115,14 @@ def build_parser():
                         '<= 2^-23); f32: the native fp32 MFMA (bitwise an fma chain).  The 3-D trainer '
                         'adds f16 / bf16: operands of the 3x3x3 convolutions rounded to f16 / bf16, fp32 accumulate (BASELINE '
                         'configs[4], tolerance 1e-2) - the 2-D kernels have no such mode and this parser rejects it')
+    p.add_argument('--act_dtype', type=str, default='f32', choices=['f32', 'f16'],
+                   help="f16: the U-Net's activations and activation gradients are stored as f16: f16 matrix cores with fp32 "
+                        "accumulation, fp32 weights / BatchNorm statistics / loss / optimizer; the heads keep fp32 tensors on fp32 "
+                        "feature maps.  Training-mode passes only (evaluation stays fp32).  Measured 9.04 against 10.87 ms per step at 16 x "
+                        "256^2 on one box (profiles/f16_2d_notes.md).  Runs without the fused ConvBlock / pooled "
+                        "BatchNorm passes of the default mode; not combined with --dense_head 1 / --revisit 1")
+    p.add_argument('--loss_scale', type=float, default=16384.0,
+                   help='--act_dtype f16: gradients enter the f16 region multiplied by this power of two')
     p.add_argument('--anchors_per_rank', type=str, default='split', choices=['split', 'full'],
                    help='data parallel only (SURVEY 8e). split: every rank samples num_queries/world anchors per class, so the '
                         'world draws the same total number of queries as the single-process reference; full: num_queries per rank')
@@ -165,7 +174,7 @@ SIDE_SYNC = int(os.environ.get("ARCO_SIDE_SYNC", "0"))
 IMG_EARLY = int(os.environ.get("ARCO_IMG_EARLY", "1"))     # see ArcoStep2D.step (with TEACHER_SIDE >= 4)
 
 
-class ArcoStep2D:
+class ArcoStep2D(LossScaleGuard):
     """State + one training step of the 2-D hot path (train_arco_2d.py:147-154,220-253,284-435)."""
 
     def __init__(self, args, device="cuda"):
@@ -177,6 +186,14 @@ class ArcoStep2D:
             raise ValueError(f"--conv_mma {mma}: the 2-D step computes in f32x3 or f32; f16 / bf16 operands are a 3-D trainer mode")
         ops.CONV_MMA = {"f32": 0, "f32x3": 3}[mma]
         ops.HEAD_MMA = 0                 # (a 3-D trainer of this process may have set the heads' reduced-precision mode)
+        # f16 activation storage of the U-Net: set BOTH ways (a default stepper built after an f16 one in the same process is fp32
+        # again), before the PackPlans - they carry the f16 packs
+        half = getattr(args, "act_dtype", "f32") == "f16"
+        if half and (getattr(args, "dense_head", 0) or getattr(args, "revisit", 0)):
+            raise ValueError("--act_dtype f16 is not combined with --dense_head 1 / --revisit 1: the dense heads and the revisiting "
+                             "term have not been run on the f16 U-Net (use --act_dtype f32)")
+        ops.ACT_HALF = half
+        ops.LOSS_SCALE = float(getattr(args, "loss_scale", 16384.0))
         if ops._WGRAD_SIDE_ENV is None:
             ops.WGRAD_SIDE = 0           # (... and the side-stream weight gradients: 11.0-11.2 -> 12.2-12.3 ms on this step)
         self.random_pool = None
@@ -226,10 +243,10 @@ class ArcoStep2D:
                   self.q_feature_extractor):
             m.train()                                                   # :263-267
         # packed conv weights: one launch per weight owner per step (ops.PackPlan), refreshed by the owner
-        plan_s = ops.PackPlan([self.model, self.q_representation, self.q_feature_extractor], True)
+        plan_s = ops.PackPlan([self.model, self.q_representation, self.q_feature_extractor], True, half=[ops.ACT_HALF, False, False])
         self.optimizer.plans = [plan_s]
         pairs = self.isd._ensure_ema_pairs()
-        pairs[0].plans = [ops.PackPlan([self.ema_model], False)]
+        pairs[0].plans = [ops.PackPlan([self.ema_model], False, half=[ops.ACT_HALF])]
         for pr in pairs[1:]:
             pr.plans = [ops.PackPlan([], False)]
         self.k_fe_ema.plans = [ops.PackPlan([self.k_feature_extractor], False)]
@@ -294,6 +311,8 @@ class ArcoStep2D:
         it, and the torch-CPU-generator index replay runs on the host while they execute."""
         a = self.args
         C = a.num_classes
+        if ops.ACT_HALF:
+            self._loss_scale_update()
         for pl in self.plans:                                            # stale only if someone else touched weights
             if not pl.valid:
                 pl.refresh()
@@ -604,7 +623,11 @@ class ArcoStep2D:
         self.optimizer.merge_second(self.heads_start)      # the warped pass's parameter gradients (replayed on the side stream)
         if zero_path:     # `0 * rep.sum()` gives EVERY head parameter a zero gradient: SGD still decays / applies momentum to them
             self.optimizer.touch_from(self.heads_start)
+        if ops.ACT_HALF:       # the U-Net's parameter gradients carry the loss scale of the f16 region
+            ok_unet = self._unscale_and_guard()
         adist.allreduce_grads(self.optimizer)
+        if ops.ACT_HALF:
+            self._guard_heads_and_publish(ok_unet)
         self.optimizer.step()
         self.isd._momentum_update_key_encoder()                          # :432
         lr_ = a.base_lr * (1.0 - self.iter_num / a.max_iterations) ** 0.9   # :433-435
@@ -711,6 +734,9 @@ def train(args, snapshot_path):
             l_img, l_lab = l_next['image'].to(dev, non_blocking=True), l_next['label'].to(dev, non_blocking=True).long()
             u_img = u_next['image'].to(dev, non_blocking=True)
         loss, reco = stepper.step(l_img, l_lab, u_img, it // iters_per_epoch, max_epoch)
+        if rank == 0 and ops.ACT_HALF and (stepper.iter_num == 1 or stepper.iter_num % 50 == 0 or stepper.iter_num == args.max_iterations):
+            logging.info('iteration %d : --act_dtype f16, loss scale %g, %d overflowed step(s) so far'
+                         % (stepper.iter_num, ops.LOSS_SCALE, stepper.overflow_steps))
         if rank == 0:
             if "loss_q" in stepper.last_terms:                          # --revisit 1: the reference's logged total (:426,457)
                 logging.info('iteration %d : loss : %f, reco_loss: %f' % (stepper.iter_num, loss.item(), reco.item()))

@@ -21,6 +21,7 @@ import torch.nn as nn
 from . import _contrast as C_
 from . import dist as adist
 from . import augment, glue, graphs, head, ops, optim
+from .loss_scale import LossScaleGuard
 from .tps.rand_tps_3d import RandTPS as RandTPS3D
 from .model_3D import ISD_3d, FeatureExtractor_3d
 from .train_arco_2d import build_parser as _build_parser_2d
@@ -55,16 +56,14 @@ def build_parser():
     p.set_defaults(patch_size=[112, 112, 80], func='asmc', k5=0.1, exp='LA/example_training', model='vnet', max_iterations=6000,
                    root_path='/home/weicheng/selfLearning/DTC/data/2018LA_Seg_Training Set')       # train_arco_3d.py:27-36
     next(a for a in p._actions if a.dest == 'conv_mma').choices = ['f32x3', 'f32', 'f16', 'bf16']   # the volume kernels' extra modes
-    p.add_argument('--act_dtype', type=str, default='f32', choices=['f32', 'f16'],
-                   help="f16: the V-Net's activations and activation gradients are stored as f16 (BASELINE configs[4], 'fp16 MFMA "
-                        "conv'): f16 matrix cores with fp32 accumulation, fp32 weights / BatchNorm statistics / loss / optimizer; "
-                        "the heads keep fp32 tensors, their GEMM operands follow --head_mma")
+    next(a for a in p._actions if a.dest == 'act_dtype').help = (
+        "f16: the V-Net's activations and activation gradients are stored as f16 (BASELINE configs[4], 'fp16 MFMA "
+        "conv'): f16 matrix cores with fp32 accumulation, fp32 weights / BatchNorm statistics / loss / optimizer; "
+        "the heads keep fp32 tensors, their GEMM operands follow --head_mma")
     p.add_argument('--head_mma', type=str, default='auto', choices=['auto', 'f32x3', 'f16', 'bf16'],
                    help="matrix-core operands of the heads' GEMMs (FeatureExtractor_3d, q_representation, the row-sparse heads).  auto: f16 "
                         "with --act_dtype f16 (BASELINE configs[4] 'fp16 MFMA conv + contrastive': operands rounded to f16 in registers, "
                         "fp32 accumulate, gradient operands bf16; the full-resolution maps are read as stored f16 rows), else --conv_mma's mode")
-    p.add_argument('--loss_scale', type=float, default=16384.0,
-                   help='--act_dtype f16: gradients enter the f16 region multiplied by this power of two')
     p.add_argument('--eqv_pass', type=int, default=1,
                    help='1: run the equivariance block of train_arco_3d.py:368-388 (warp + one more student forward); '
                         'its loss only enters the objective at iteration 0 there (:390-393), afterwards it is a logged '
@@ -72,7 +71,7 @@ def build_parser():
     return p
 
 
-class ArcoStep3D:
+class ArcoStep3D(LossScaleGuard):
     """State + one training step of the 3-D hot path (train_arco_3d.py:144-151,195-232,257-415)."""
 
     def __init__(self, args, device="cuda"):
@@ -157,75 +156,6 @@ class ArcoStep3D:
         # the warped student pass carries no gradient after iteration 0 (:390-393): replayed as one graph - its ~300 eager
         # launches sat right behind the sampler stage, the stretch of the step where the GPU waits for the host
         self.s_fwd_tps = graphs.GraphedForward(self.model, enabled=use_graphs)
-
-    def _unscale_and_guard(self):
-        """--act_dtype f16: divide the loss scale out of the V-Net's stretch of the flat gradient and guard the step against an
-        overflow of the f16 backward (an inf / NaN in flat_g would go straight into SGD, the EMA teacher and,
-        a step later, the memory banks - silently and for good).  All on the device, no host synchronisation in the step:
-        `ok` = every V-Net gradient finite (on every rank); non-finite values are replaced by zeros and the V-Net's gradient is multiplied
-        by ok, so an overflowed step leaves the V-Net with weight decay and momentum only instead of poisoning the run (the heads' fp32
-        gradients do not pass through the f16 backward; they are guarded behind their all-reduce: _guard_heads_and_publish).
-        The flag is copied to pinned memory and read at the START of the next step (long complete by then): an overflow halves
-        the loss scale (floor 1), 500 clean steps double it again up to --loss_scale (dynamic loss scaling)."""
-        gv = self.optimizer.flat_g[:self.heads_start]
-        gv.mul_(1.0 / ops.LOSS_SCALE)
-        ok = torch.isfinite(gv).all()
-        torch.nan_to_num_(gv, nan=0.0, posinf=0.0, neginf=0.0)
-        okf = ok.to(torch.float32).view(1)
-        if adist.is_dist():
-            # every rank must take the same decision (a rank that zeroed alone would leave the replicas' loss scales, graphs and -
-            # through momentum - weights apart): MIN over ranks, issued by every rank every f16 step, in front of the V-Net bucket
-            adist.allreduce_min(okf)
-        # Only the V-Net's stretch is written: the heads' gradients are fp32, produced UPSTREAM of the f16 backward (always
-        # finite), and under data parallelism their bucket flat_g[heads_start:] is already inside an asynchronous all-reduce
-        # started by dist.mark_heads_done's backward hook - nothing may write it before allreduce_grads has waited (ADVICE r4).
-        gv.mul_(okf)
-        return okf > 0
-
-    def _guard_heads_and_publish(self, ok):
-        """Second half of the guard, AFTER allreduce_grads has waited for the heads' bucket: an f16 forward overflow (an inf
-        in a feature-map row or in the loss) makes the heads' fp32 gradients NaN although they never pass through the f16 backward.
-        The reduced bucket is identical on every rank, so every rank takes the same decision without another collective: non-finite
-        values -> zeros, the bucket multiplied by its own finite flag, and the flag folded into the overflow flag that drives the
-        dynamic loss scale (copied to pinned memory, read at the start of the next step)."""
-        gh = self.optimizer.flat_g[self.heads_start:]
-        okh = torch.isfinite(gh).all()
-        torch.nan_to_num_(gh, nan=0.0, posinf=0.0, neginf=0.0)
-        gh.mul_(okh.to(torch.float32))
-        ok = ok.view(1) & okh.view(1)
-        if self._ovf_host is None:
-            self._ovf_host = torch.ones(1, dtype=torch.bool).pin_memory()
-        self._ovf_host.copy_(ok, non_blocking=True)
-        self._ovf_event = torch.cuda.Event()
-        self._ovf_event.record()
-
-    def _loss_scale_update(self):
-        """Host side of the guard: consume last step's flag (see _unscale_and_guard)."""
-        ev = self._ovf_event
-        if ev is None:
-            return
-        ev.synchronize()              # recorded a whole step ago: returns at once
-        self._ovf_event = None
-        if not bool(self._ovf_host[0]):
-            self.overflow_steps += 1
-            self._clean_steps = 0
-            ops.LOSS_SCALE = max(1.0, ops.LOSS_SCALE / 2.0)
-            self._recapture_train_graphs()
-            logging.warning("f16 backward overflowed at iteration %d: step reduced to a zero-gradient step, loss scale -> %g",
-                            self.iter_num - 1, ops.LOSS_SCALE)
-        else:
-            self._clean_steps += 1
-            if self._clean_steps >= 500 and ops.LOSS_SCALE < float(getattr(self.args, "loss_scale", 16384.0)):
-                ops.LOSS_SCALE *= 2.0
-                self._clean_steps = 0
-                self._recapture_train_graphs()
-
-    def _recapture_train_graphs(self):
-        """The loss scale is a kernel argument of the boundary cast inside the captured backward graphs: a new scale needs a
-        new capture (the next call of each GraphedTrain re-captures; rare)."""
-        for v in vars(self).values():
-            if isinstance(v, graphs.GraphedTrain):
-                v.captured = False
 
     @staticmethod
     def _lazy_teacher(kfe, fm_t):

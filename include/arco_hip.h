@@ -496,6 +496,27 @@ int arco_d2s3_add(const float* P, long ldp, int NV, int X2, int Y2, int Z2, int 
 int arco_d2s3_add_h(const void* P, long ldp, int NV, int X2, int Y2, int Z2, int C, const void* ADD, long lda, void* V, long ldv, void* stream);
 int arco_cast_h2f(const void* x, long n, float* y, void* stream);
 int arco_cast_f2h(const float* x, long n, float scale, void* y, void* stream);
+/* f16 activation storage on the 2-D path (train_arco_2d --act_dtype f16; csrc/unet_h.hip).  The 3x3 convolutions of f16 maps run
+ * through arco_conv3d_fwd / arco_conv3d_wgrad(taps = 9, D3 = 1, mma = 4): hconv_kernel's plane step without the depth loop, rows
+ * that are not whole 16-byte pieces (the gradient of a 4- / 19-class out_conv) staged element-wise.
+ *   arco_conv3x3_image_fwd_h:    the first layer - fp32 image (K <= 4 channels, the fp32 forward pack [9][16][16]) -> f16 map of
+ *                                N <= 16 channels + BatchNorm partials of the rounded values, one slab per workgroup
+ *                                (arco_conv3x3_image_mblocks_h of them).
+ *   arco_conv3x3_image_wgrad_h:  its weight gradient from the f16 dZ (16 channels) and the fp32 image; ws as arco_wgrad_ws_floats.
+ *   arco_maxpool2_*_h / arco_bilinear_*_h: the fp32 entry points of the same name on f16 tensors (C % 8 == 0, rows of whole
+ *                                16-byte pieces): fp32 arithmetic, one rounding on store.                                       */
+int arco_conv3x3_image_mblocks_h(int NB, int H, int W, int stat_groups);
+int arco_conv3x3_image_fwd_h(const float* in, long ld_in, int K, const float* Wp, int N, void* out, long ld_out, const float* bias,
+                             float* stat_sum, float* stat_sq, int NB, int H, int W, int stat_groups, void* stream);
+int arco_conv3x3_image_wgrad_h(const void* dZ, long ld_dz, int Cout, const float* in, long ld_in, int K, int NB, int H, int W,
+                               float* ws, float* dW, int accumulate, void* stream);
+int arco_maxpool2_fwd_h(const void* X, long ldx, int NB, int H, int W, int C, void* Y, long ldy, void* stream);
+int arco_maxpool2_bwd_h(const void* X, long ldx, int NB, int H, int W, int C, const void* dY, long ldy, void* dX, long ldo,
+                        void* stream);
+int arco_maxpool2_bwd_add_h(const void* X, long ldx, int NB, int H, int W, int C, const void* dY, long ldy, const void* add,
+                            long ld_add, void* dX, long ldo, void* stream);
+int arco_bilinear_fwd_h(const void* X, long ldx, int NB, int Hi, int Wi, int C, int Ho, int Wo, void* Y, long ldy, void* stream);
+int arco_bilinear_bwd_h(const void* dY, long ldy, int NB, int Hi, int Wi, int C, int Ho, int Wo, void* dX, long ldx, void* stream);
 
 #ifdef __cplusplus
 }
