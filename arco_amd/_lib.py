@@ -101,6 +101,8 @@ _SIGS = {
     "arco_up_neighbors": [_P, _L, _I, _I, _I, _I, _P, _P, _P],
     "arco_lerp4_cat_rows": [_P, _L, _I, _P, _P, _L, _I, _P, _L, _P, _L, _P],
     "arco_lerp4_cat_rows_bwd": [_P, _L, _I, _P, _P, _L, _P, _L, _P, _L, _I, _P],
+    "arco_gather_upcat_rows_h": [_P, _L, _I, _I, _I, _P, _L, _I, _I, _I, _P, _L, _P, _L, _P],
+    "arco_lerp4_cat_rows_h": [_P, _L, _I, _P, _P, _L, _I, _P, _L, _P, _L, _P],
     "arco_s2d3": [_P, _L, _I, _I, _I, _I, _I, _P, _L, _I, _P],
     "arco_trilinear_fwd": [_P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P],
     "arco_trilinear_bwd": [_P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P],

@@ -626,8 +626,11 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
 // For anchor j with high-res pixel id pix[j] = (n, y, x):  X[j][0..Clo) = align_corners bilinear
 // sample of `lo` at (y, x) (same fp32 index math / lerp order as bilinear_fwd_kernel, so rows are
 // bit-identical to the dense upsample+cat), X[j][Clo..Clo+Chi) = hi[pix[j]].
+// TH = _Float16: `hi` stored as f16 (f16 activation storage, --fm_rows f16) - four channels per 8-byte load, widened in registers
+// (exact), so the rows equal those of the fp32 kernel on the upcast map bit for bit.
+template <typename TH>
 __global__ __launch_bounds__(256) void gather_upcat_rows_kernel(const float* __restrict__ lo, long ldlo, int Clo, int Hi, int Wi,
-                                                               const float* __restrict__ hi, long ldhi, int Chi, int Ho, int Wo,
+                                                               const TH* __restrict__ hi, long ldhi, int Chi, int Ho, int Wo,
                                                                const int64_t* __restrict__ pix, long n, float* __restrict__ X, long ldx) {
   const int lane = threadIdx.x & 63;
   const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -651,8 +654,8 @@ __global__ __launch_bounds__(256) void gather_upcat_rows_kernel(const float* __r
     for (int e = 0; e < 4; ++e) r[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
     *reinterpret_cast<f32x4*>(o + c) = r;
   }
-  const float* h = hi + p * ldhi;
-  for (int c = lane * 4; c < Chi; c += 256) *reinterpret_cast<f32x4*>(o + Clo + c) = *reinterpret_cast<const f32x4*>(h + c);
+  const TH* h = hi + p * ldhi;
+  for (int c = lane * 4; c < Chi; c += 256) *reinterpret_cast<f32x4*>(o + Clo + c) = ld4f(h + c);
 }
 __global__ __launch_bounds__(256) void scatter_upcat_rows_kernel(const float* __restrict__ dX, long ldx, const int64_t* __restrict__ pix, long n,
                                                                 float* __restrict__ dlo, long ldlo, int Clo, int Hi, int Wi,
@@ -699,8 +702,10 @@ __global__ void up_neighbors_kernel(const int64_t* __restrict__ pix, long n, int
 }
 // X[j][0..Clo) = hy*(hx*V[4j]+lx*V[4j+1]) + ly*(hx*V[4j+2]+lx*V[4j+3])  (same order as bilinear_fwd_kernel);
 // X[j][Clo..Clo+Chi) = hi[pix[j]]
+// (TH = _Float16: `hi` stored as f16, as in gather_upcat_rows_kernel)
+template <typename TH>
 __global__ __launch_bounds__(256) void lerp4_cat_rows_kernel(const float* __restrict__ V, long ldv, int Clo,
-                                                            const float* __restrict__ lylx, const float* __restrict__ hi,
+                                                            const float* __restrict__ lylx, const TH* __restrict__ hi,
                                                             long ldhi, int Chi, const int64_t* __restrict__ pix, long n,
                                                             float* __restrict__ X, long ldx) {
   const int lane = threadIdx.x & 63;
@@ -717,8 +722,8 @@ __global__ __launch_bounds__(256) void lerp4_cat_rows_kernel(const float* __rest
     for (int e = 0; e < 4; ++e) r[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
     *reinterpret_cast<f32x4*>(o + c) = r;
   }
-  const float* h = hi + pix[j] * ldhi;
-  for (int c = lane * 4; c < Chi; c += 256) *reinterpret_cast<f32x4*>(o + Clo + c) = *reinterpret_cast<const f32x4*>(h + c);
+  const TH* h = hi + pix[j] * ldhi;
+  for (int c = lane * 4; c < Chi; c += 256) *reinterpret_cast<f32x4*>(o + Clo + c) = ld4f(h + c);
 }
 // adjoint: dV[4j+t] = w_t * dX[j][0..Clo) ; dhi[pix[j]] += dX[j][Clo..)
 __global__ __launch_bounds__(256) void lerp4_cat_rows_bwd_kernel(const float* __restrict__ dX, long ldx, int Clo,
@@ -1383,8 +1388,17 @@ int arco_gather_upcat_rows(const float* lo, long ldlo, int Clo, int Hi, int Wi, 
                            int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream) {
   ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldlo & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
-  hipLaunchKernelGGL(gather_upcat_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), lo, ldlo, Clo, Hi, Wi,
+  hipLaunchKernelGGL(gather_upcat_rows_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), lo, ldlo, Clo, Hi, Wi,
                      hi, ldhi, Chi, Ho, Wo, pix, n, X, ldx);
+  return arco_launch_status();
+}
+// ... with the map `hi` stored as f16 (f16 activation storage of the U-Net, --fm_rows f16); lo, X fp32.  ldhi in f16 elements.
+int arco_gather_upcat_rows_h(const float* lo, long ldlo, int Clo, int Hi, int Wi, const void* hi, long ldhi, int Chi,
+                             int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream) {
+  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldlo & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  if (n == 0) return ARCO_OK;
+  hipLaunchKernelGGL(gather_upcat_rows_kernel<_Float16>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), lo, ldlo, Clo, Hi, Wi,
+                     reinterpret_cast<const _Float16*>(hi), ldhi, Chi, Ho, Wo, pix, n, X, ldx);
   return arco_launch_status();
 }
 int arco_scatter_upcat_rows(const float* dX, long ldx, const int64_t* pix, long n, float* dlo, long ldlo, int Clo, int Hi,
@@ -1404,8 +1418,16 @@ int arco_lerp4_cat_rows(const float* V, long ldv, int Clo, const float* lylx, co
                         const int64_t* pix, long n, float* X, long ldx, void* stream) {
   ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
-  hipLaunchKernelGGL(lerp4_cat_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), V, ldv, Clo, lylx, hi, ldhi,
+  hipLaunchKernelGGL(lerp4_cat_rows_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), V, ldv, Clo, lylx, hi, ldhi,
                      Chi, pix, n, X, ldx);
+  return arco_launch_status();
+}
+int arco_lerp4_cat_rows_h(const float* V, long ldv, int Clo, const float* lylx, const void* hi, long ldhi, int Chi,
+                          const int64_t* pix, long n, float* X, long ldx, void* stream) {
+  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  if (n == 0) return ARCO_OK;
+  hipLaunchKernelGGL(lerp4_cat_rows_kernel<_Float16>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), V, ldv, Clo, lylx,
+                     reinterpret_cast<const _Float16*>(hi), ldhi, Chi, pix, n, X, ldx);
   return arco_launch_status();
 }
 int arco_lerp4_cat_rows_bwd(const float* dX, long ldx, int Clo, const float* lylx, const int64_t* pix, long n, float* dV,

@@ -123,7 +123,7 @@ class GraphedTrain:
     def will_replay(self, x):
         """Will the next call with input x capture-or-replay the graphs (rather than run the module eagerly)?"""
         return (self.enabled and self.calls >= self.warmup and torch.is_grad_enabled()
-                and (not self.captured or tuple(x.shape) == self.shape))
+                and (not self.captured or (tuple(x.shape) == self.shape and ops.FM_CAST == self.fm_cast)))
 
     def _capture(self, x):
         from torch.utils import _pytree as pytree
@@ -195,6 +195,7 @@ class GraphedTrain:
             ops.SEED_DEV = prev_salt
         self.captured = True
         self.shape = tuple(x.shape)
+        self.fm_cast = ops.FM_CAST         # the boundary-cast mode is baked into both graphs (which outputs are f16, which casts run)
 
     def __call__(self, x):
         self.calls += 1
@@ -202,7 +203,7 @@ class GraphedTrain:
             return self.module(x)
         if not self.captured:
             self._capture(x)
-        if tuple(x.shape) != self.shape:
+        if tuple(x.shape) != self.shape or ops.FM_CAST != self.fm_cast:
             return self.module(x)
         from torch.utils import _pytree as pytree
         outs = _GraphedTrainFn.apply(self, x, *self.params)

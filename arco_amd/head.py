@@ -41,6 +41,25 @@ def _wgrad(dy, x, like):
     return ops.conv_wgrad(dy, dy.stride(0), int(dy.shape[1]), x, x.stride(0), int(x.shape[1]), 1, 1, 1, n, like)
 
 
+def _h(name, t):
+    """entry point `name` for a feature map read as rows: its f16-`hi` form when the map is stored as f16 (ops.fm_rows_half)."""
+    return name + "_h" if t.dtype == torch.float16 else name
+
+
+def _fm_grad_buffer(half, ptr, shape, dev):
+    """(fp32 scatter target [nb, *spatial, c], done(idx, n) -> the gradient to hand back) of a feature map read as rows: the f16
+    form of the producer's gradient carrying ops.LOSS_SCALE for a map stored as f16 (_row_grad_buffer_h), else the target itself
+    (_row_grad_buffer)."""
+    if half:
+        return _row_grad_buffer_h(ptr, shape, dev)
+    buf, fin = _row_grad_buffer(ptr, shape, dev)
+
+    def done(idx, n):
+        fin(idx, n)
+        return buf
+    return buf, done
+
+
 class LazyHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x3p, f4, w4, w1, w2, pix):
@@ -50,13 +69,15 @@ class LazyHeadFn(torch.autograd.Function):
         chi, ho, wo = int(f4.shape[1]), int(f4.shape[2]), int(f4.shape[3])
         n = int(pix.shape[0])
         X = torch.empty((n, clo + chi), dtype=torch.float32, device=x3p.device)
-        L.call("arco_gather_upcat_rows", L.ptr(lo), ldlo, clo, hi_h, hi_w, L.ptr(hi), ldhi, chi, ho, wo, L.ptr(pix), n,
+        L.call(_h("arco_gather_upcat_rows", hi), L.ptr(lo), ldlo, clo, hi_h, hi_w, L.ptr(hi), ldhi, chi, ho, wo, L.ptr(pix), n,
                L.ptr(X), clo + chi)
         h0 = _gemm(X, w4)
         h1 = _gemm(h0, w1)
         a = _gemm(h1, w2)
         ctx.save_for_backward(X, h0, h1, w4, w1, w2, pix)
         ctx.geom = (nb, clo, hi_h, hi_w, chi, ho, wo)
+        ctx.fptrs = (f4.data_ptr(),)
+        ctx.fhalf = (f4.dtype == torch.float16,)      # ops.fm_rows_half: map consumed as stored
         return a
 
     @staticmethod
@@ -70,9 +91,11 @@ class LazyHeadFn(torch.autograd.Function):
         dh0 = _gemm_t(dh1, w1)
         dw4 = _wgrad(dh0, X, w4)
         dX = _gemm_t(dh0, w4)
+        n = int(pix.shape[0])
         dlo = torch.zeros((nb, hi_h, hi_w, clo), dtype=torch.float32, device=da.device)
-        dhi = torch.zeros((nb, ho, wo, chi), dtype=torch.float32, device=da.device)
-        _scatter_upcat2d(dX, clo + chi, pix, int(pix.shape[0]), dlo, clo, hi_h, hi_w, dhi, chi, ho, wo)
+        dhi, done = _fm_grad_buffer(ctx.fhalf[0], ctx.fptrs[0], (nb, chi, ho, wo), da.device)
+        _scatter_upcat2d(dX, clo + chi, pix, n, dlo, clo, hi_h, hi_w, dhi, chi, ho, wo)
+        dhi = done(pix, n)
         return dlo.permute(0, 3, 1, 2), dhi.permute(0, 3, 1, 2), dw4, dw1, dw2, None
 
 
@@ -97,13 +120,13 @@ def _rows2d_forward(x2p, f3, f4, w3, w4, pix):
     L.call("arco_up_neighbors", L.ptr(pix), n, h3, w3_, h4, w4_, L.ptr(nb4), L.ptr(lylx))
     k3 = c2 + c3
     X3 = torch.empty((4 * n, k3), dtype=torch.float32, device=dev)
-    L.call("arco_gather_upcat_rows", L.ptr(lo2), ld2, c2, h2, w2_, L.ptr(r3), ld3, c3, h3, w3_, L.ptr(nb4), 4 * n,
+    L.call(_h("arco_gather_upcat_rows", r3), L.ptr(lo2), ld2, c2, h2, w2_, L.ptr(r3), ld3, c3, h3, w3_, L.ptr(nb4), 4 * n,
            L.ptr(X3), k3)
     y3, _ = ops.conv_raw(X3, k3, k3, ops.pack_weight(w3, 1, 0), k3, 1, 1, 4 * n, 1, residual=X3, ld_res=k3)
     X3p = y3.permute(0, 2, 3, 1).reshape(4 * n, k3)                     # fea3(x)+x rows
     k4 = k3 + c4
     X4 = torch.empty((n, k4), dtype=torch.float32, device=dev)
-    L.call("arco_lerp4_cat_rows", L.ptr(X3p), k3, k3, L.ptr(lylx), L.ptr(r4), ld4, c4, L.ptr(pix), n, L.ptr(X4), k4)
+    L.call(_h("arco_lerp4_cat_rows", r4), L.ptr(X3p), k3, k3, L.ptr(lylx), L.ptr(r4), ld4, c4, L.ptr(pix), n, L.ptr(X4), k4)
     return X3, X4, nb4, lylx, _gemm(X4, w4)
 
 
@@ -123,6 +146,8 @@ class LazyHead2Fn(torch.autograd.Function):
         a = _gemm(h1, w2)
         ctx.save_for_backward(X3, X4, h0, h1, w3, w4, w1, w2, pix, nb4, lylx)
         ctx.geom = (nb, c2, h2, w2_, c3, h3, w3_, c4, h4, w4_)
+        ctx.fptrs = (f3.data_ptr(), f4.data_ptr())
+        ctx.fhalf = (f3.dtype == torch.float16, f4.dtype == torch.float16)      # ops.fm_rows_half: maps consumed as stored
         return a
 
     @staticmethod
@@ -140,15 +165,17 @@ class LazyHead2Fn(torch.autograd.Function):
         dw4 = _wgrad(dh0, X4, w4)
         dX4 = _gemm_t(dh0, w4)
         dX3p = torch.empty((4 * n, k3), dtype=torch.float32, device=dev)
-        df4 = torch.zeros((nb, h4, w4_, c4), dtype=torch.float32, device=dev)
+        df4, done4 = _fm_grad_buffer(ctx.fhalf[1], ctx.fptrs[1], (nb, c4, h4, w4_), dev)
         _lerp4_cat_rows_bwd(dX4, k3 + c4, k3, lylx, pix, n, dX3p, df4, c4)
+        df4 = done4(pix, n)
         dw3 = _wgrad(dX3p, X3, w3)
         # d(fea3(x)+x)/dx: W3^T dy + dy  (residual fused in the dgrad GEMM epilogue)
         y, _ = ops.conv_raw(dX3p, k3, k3, ops.pack_weight(w3, 1, 1), k3, 1, 1, 4 * n, 1, residual=dX3p, ld_res=k3)
         dX3 = y.permute(0, 2, 3, 1).reshape(4 * n, k3)
         dx2p = torch.zeros((nb, h2, w2_, c2), dtype=torch.float32, device=dev)
-        df3 = torch.zeros((nb, h3, w3_, c3), dtype=torch.float32, device=dev)
+        df3, done3 = _fm_grad_buffer(ctx.fhalf[0], ctx.fptrs[0], (nb, c3, h3, w3_), dev)
         _scatter_upcat2d(dX3, k3, nb4, 4 * n, dx2p, c2, h2, w2_, df3, c3, h3, w3_)
+        df3 = done3(nb4, 4 * n)
         return (dx2p.permute(0, 3, 1, 2), df3.permute(0, 3, 1, 2), df4.permute(0, 3, 1, 2), dw3, dw4, dw1, dw2, None)
 
 
@@ -185,14 +212,14 @@ def _rows3lvl_forward(x1p, f2, f3, f4, w2, w3, w4, pix):
     L.call("arco_up_neighbors", L.ptr(nb4), 4 * n, h2, w2_, h3, w3_, L.ptr(nb16), L.ptr(lylx3))
     k2, k3, k4 = c1 + c2, c1 + c2 + c3, c1 + c2 + c3 + c4
     X2 = torch.empty((16 * n, k2), dtype=torch.float32, device=dev)
-    L.call("arco_gather_upcat_rows", L.ptr(lo1), ld1, c1, h1, w1_, L.ptr(r2), ld2, c2, h2, w2_, L.ptr(nb16), 16 * n,
+    L.call(_h("arco_gather_upcat_rows", r2), L.ptr(lo1), ld1, c1, h1, w1_, L.ptr(r2), ld2, c2, h2, w2_, L.ptr(nb16), 16 * n,
            L.ptr(X2), k2)
     X2p = _fea_rows(X2, w2, 0)
     X3 = torch.empty((4 * n, k3), dtype=torch.float32, device=dev)
-    L.call("arco_lerp4_cat_rows", L.ptr(X2p), k2, k2, L.ptr(lylx3), L.ptr(r3), ld3, c3, L.ptr(nb4), 4 * n, L.ptr(X3), k3)
+    L.call(_h("arco_lerp4_cat_rows", r3), L.ptr(X2p), k2, k2, L.ptr(lylx3), L.ptr(r3), ld3, c3, L.ptr(nb4), 4 * n, L.ptr(X3), k3)
     X3p = _fea_rows(X3, w3, 0)
     X4 = torch.empty((n, k4), dtype=torch.float32, device=dev)
-    L.call("arco_lerp4_cat_rows", L.ptr(X3p), k3, k3, L.ptr(lylx4), L.ptr(r4), ld4, c4, L.ptr(pix), n, L.ptr(X4), k4)
+    L.call(_h("arco_lerp4_cat_rows", r4), L.ptr(X3p), k3, k3, L.ptr(lylx4), L.ptr(r4), ld4, c4, L.ptr(pix), n, L.ptr(X4), k4)
     return X2, X3, X4, nb4, nb16, lylx3, lylx4, _gemm(X4, w4)
 
 
@@ -327,6 +354,7 @@ class LazyHead3Fn(torch.autograd.Function):
         a = _gemm(hh, wq2)
         ctx.save_for_backward(X2, X3, X4, h0, hh, w2, w3, w4, w1, wq2, pix, nb4, nb16, lylx3, lylx4)
         ctx.fptrs = (f2.data_ptr(), f3.data_ptr(), f4.data_ptr())
+        ctx.fhalf = (f2.dtype == torch.float16, f3.dtype == torch.float16, f4.dtype == torch.float16)      # ops.fm_rows_half
         ctx.geom = (int(x1p.shape[0]), int(x1p.shape[1]), int(x1p.shape[2]), int(x1p.shape[3]),
                     int(f2.shape[1]), int(f2.shape[2]), int(f2.shape[3]), int(f3.shape[1]), int(f3.shape[2]), int(f3.shape[3]),
                     int(f4.shape[1]), int(f4.shape[2]), int(f4.shape[3]))
@@ -347,21 +375,21 @@ class LazyHead3Fn(torch.autograd.Function):
         dw4 = _wgrad(dh0, X4, w4)
         dX4 = _gemm_t(dh0, w4)
         dX3p = torch.empty((4 * n, k3), dtype=torch.float32, device=dev)
-        df4, fin4 = _row_grad_buffer(ctx.fptrs[2], (nb, c4, h4, w4_), dev)
+        df4, done4 = _fm_grad_buffer(ctx.fhalf[2], ctx.fptrs[2], (nb, c4, h4, w4_), dev)
         _lerp4_cat_rows_bwd(dX4, k3 + c4, k3, lylx4, pix, n, dX3p, df4, c4)
-        fin4(pix, n)
+        df4 = done4(pix, n)
         dw3 = _wgrad(dX3p, X3, w3)
         dX3 = _fea_rows(dX3p, w3, 1)
         dX2p = torch.empty((16 * n, k2), dtype=torch.float32, device=dev)
-        df3, fin3 = _row_grad_buffer(ctx.fptrs[1], (nb, c3, h3, w3_), dev)
+        df3, done3 = _fm_grad_buffer(ctx.fhalf[1], ctx.fptrs[1], (nb, c3, h3, w3_), dev)
         _lerp4_cat_rows_bwd(dX3, k3, k2, lylx3, nb4, 4 * n, dX2p, df3, c3)
-        fin3(nb4, 4 * n)
+        df3 = done3(nb4, 4 * n)
         dw2 = _wgrad(dX2p, X2, w2)
         dX2 = _fea_rows(dX2p, w2, 1)
         dx1p = torch.zeros((nb, h1, w1_, c1), dtype=torch.float32, device=dev)
-        df2, fin2 = _row_grad_buffer(ctx.fptrs[0], (nb, c2, h2, w2_), dev)
+        df2, done2 = _fm_grad_buffer(ctx.fhalf[0], ctx.fptrs[0], (nb, c2, h2, w2_), dev)
         _scatter_upcat2d(dX2, k2, nb16, 16 * n, dx1p, c1, h1, w1_, df2, c2, h2, w2_)
-        fin2(nb16, 16 * n)
+        df2 = done2(nb16, 16 * n)
         return (dx1p.permute(0, 3, 1, 2), df2.permute(0, 3, 1, 2), df3.permute(0, 3, 1, 2), df4.permute(0, 3, 1, 2),
                 dw2, dw3, dw4, dw1, dwq2, None)
 
@@ -415,7 +443,7 @@ class LazyTeacher2D:
         chi, ho, wo = int(self.f4.shape[1]), int(self.f4.shape[2]), int(self.f4.shape[3])
         n = int(pix.shape[0])
         X = torch.empty((n, clo + chi), dtype=torch.float32, device=pix.device)
-        L.call("arco_gather_upcat_rows", L.ptr(lo), ldlo, clo, hi_h, hi_w, L.ptr(hi), ldhi, chi, ho, wo, L.ptr(pix), n,
+        L.call(_h("arco_gather_upcat_rows", hi), L.ptr(lo), ldlo, clo, hi_h, hi_w, L.ptr(hi), ldhi, chi, ho, wo, L.ptr(pix), n,
                L.ptr(X), clo + chi)
         return _gemm(X, self.w4)
 

@@ -197,6 +197,10 @@ class Decoder(nn.Module):
         # f16 activation storage (ops.ACT_HALF, training mode): the logits and the feature maps leave the f16 region as fp32 - heads,
         # losses and samplers are fp32; gradients come back through the same boundary with the loss scale
         # (inside `with ops.logits_only():` the maps are handed out as stored, as the V-Net's are)
+        # (inside `with ops.fm_rows_half(k):` the k finest maps are handed out as stored, for the row-sparse heads)
+        if isinstance(ops.FM_CAST, tuple):
+            n_cast = len(feature_map) - ops.FM_CAST[1]
+            return ops.from_half(output), [ops.from_half(f) for f in feature_map[:n_cast]] + feature_map[n_cast:]
         return ops.from_half(output), ([ops.from_half(f) for f in feature_map] if ops.FM_CAST else feature_map)
 
 

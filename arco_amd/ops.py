@@ -1728,7 +1728,7 @@ def from_half(x):
     return _FromHalfFn.apply(x) if _is_half(x) else x
 
 
-FM_CAST = True        # True | False (logits_only) | 'lowres' (fm_rows_half)
+FM_CAST = True        # True | False (logits_only) | 'lowres' (fm_rows_half) | ('keep', k) (fm_rows_half(k): the U-Net's k finest maps)
 
 
 class logits_only:
@@ -1748,11 +1748,22 @@ class fm_rows_half(logits_only):
     """`with ops.fm_rows_half():` - a V-Net forward inside (f16 mode) casts its three LOW-resolution feature maps to fp32 and hands
     the two full-resolution ones out as stored (f16): the row-sparse heads (arco_amd.head.lazy_head3d, LazyTeacher3D) read rows /
     weighted row sums of those two straight from the f16 maps and return a row-sparse f16 gradient - no dense cast of a
-    full-resolution map in either direction (they were 0.64 ms of the LiTS-shaped step)."""
+    full-resolution map in either direction (they were 0.64 ms of the LiTS-shaped step).
+
+    `with ops.fm_rows_half(k):` - a U-Net forward inside (f16 mode) hands its k finest feature maps out as stored and casts the
+    others (and the bottleneck) to fp32: the 2-D row-sparse heads (arco_amd.head.lazy_head / lazy_head2 / lazy_head3 and the
+    lazy teachers) read rows of exactly the maps their depth never touches densely (train_arco_2d --fm_rows f16).  The count
+    travels in FM_CAST as ('keep', k) - a tuple, since 1 == True would alias the default in the graphs' capture keys; the V-Net
+    reads any value other than 'lowres' / False as "cast all"."""
+
+    def __init__(self, keep=None):
+        if keep is not None and not 1 <= int(keep) <= 4:
+            raise ValueError(f"fm_rows_half({keep}): the U-Net keeps 1..4 of its five maps as f16 (the bottleneck leaves as fp32)")
+        self.mode = 'lowres' if keep is None else ('keep', int(keep))
 
     def __enter__(self):
         global FM_CAST
-        self.prev, FM_CAST = FM_CAST, 'lowres'
+        self.prev, FM_CAST = FM_CAST, self.mode
 
 
 def space_to_depth3(x):

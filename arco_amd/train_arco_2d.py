@@ -118,9 +118,15 @@ def build_parser():
     p.add_argument('--act_dtype', type=str, default='f32', choices=['f32', 'f16'],
                    help="f16: the U-Net's activations and activation gradients are stored as f16: f16 matrix cores with fp32 "
                         "accumulation, fp32 weights / BatchNorm statistics / loss / optimizer; the heads keep fp32 tensors on fp32 "
-                        "feature maps.  Training-mode passes only (evaluation stays fp32).  Measured 9.04 against 10.87 ms per step at 16 x "
+                        "feature maps (--fm_rows f16: on f16 rows of the finest maps).  Training-mode passes only (evaluation stays fp32).  Measured 9.04 against 10.87 ms per step at 16 x "
                         "256^2 on one box (profiles/f16_2d_notes.md).  Runs without the fused ConvBlock / pooled "
                         "BatchNorm passes of the default mode; not combined with --dense_head 1 / --revisit 1")
+    p.add_argument('--fm_rows', type=str, default='f32', choices=['f32', 'f16'],
+                   help="f16 (with --act_dtype f16): the row-sparse heads read the U-Net's finest feature maps as stored - f16 rows, "
+                        "f16 row-sparse gradients rounded once from fp32 sums - instead of dense fp32 copies (the student's --head_levels "
+                        "finest maps; the teacher's finest --teacher_levels, 1 with --head_levels 1), and the three passes of the step that "
+                        "read only the logits cast no map at all.  The low-resolution maps and the logits stay fp32.  Not combined with "
+                        "--dense_head 1 / --dense_teacher 1 / --revisit 1.  Figures: profiles/f16_2d_notes.md")
     p.add_argument('--loss_scale', type=float, default=16384.0,
                    help='--act_dtype f16: gradients enter the f16 region multiplied by this power of two')
     p.add_argument('--anchors_per_rank', type=str, default='split', choices=['split', 'full'],
@@ -189,6 +195,14 @@ class ArcoStep2D(LossScaleGuard):
         # f16 activation storage of the U-Net: set BOTH ways (a default stepper built after an f16 one in the same process is fp32
         # again), before the PackPlans - they carry the f16 packs
         half = getattr(args, "act_dtype", "f32") == "f16"
+        rows16 = getattr(args, "fm_rows", "f32") == "f16"
+        if rows16 and not half:
+            raise ValueError("--fm_rows f16 needs --act_dtype f16: with fp32 activation storage there is no f16 feature map to read rows of")
+        if rows16:
+            for flag in ("dense_head", "revisit", "dense_teacher"):
+                if getattr(args, flag, 0):
+                    raise ValueError(f"--fm_rows f16 is not combined with --{flag} 1: the dense heads read whole fp32 feature maps "
+                                     f"(use --fm_rows f32)")
         if half and (getattr(args, "dense_head", 0) or getattr(args, "revisit", 0)):
             raise ValueError("--act_dtype f16 is not combined with --dense_head 1 / --revisit 1: the dense heads and the revisiting "
                              "term have not been run on the f16 U-Net (use --act_dtype f32)")
@@ -251,6 +265,15 @@ class ArcoStep2D(LossScaleGuard):
             pr.plans = [ops.PackPlan([], False)]
         self.k_fe_ema.plans = [ops.PackPlan([self.k_feature_extractor], False)]
         self.plans = [plan_s] + [pl for pr in pairs for pl in pr.plans] + self.k_fe_ema.plans
+        # --fm_rows f16: how many of its finest maps a pass hands out as stored (ops.fm_rows_half(k)) - exactly those its consumer
+        # reads as rows only (FeatureExtractor.forward_lowres / _lowres2 / _lowres1 run fp32 GEMMs on the others); the passes that
+        # read nothing but the logits cast no map (ops.logits_only).  --fm_rows f32: every pass casts all five, as before.
+        hl = getattr(args, "head_levels", 3)
+        self.fm_keep_s = (1 if hl == 1 else 3 if hl == 3 else 2) if rows16 else 0
+        self.fm_keep_t = (1 if hl == 1 else 3 if getattr(args, "teacher_levels", 2) == 3 else 2) if rows16 else 0
+        self._fm_s = (lambda: ops.fm_rows_half(self.fm_keep_s)) if rows16 else contextlib.nullcontext
+        self._fm_t = (lambda: ops.fm_rows_half(self.fm_keep_t)) if rows16 else contextlib.nullcontext
+        self._fm_none = ops.logits_only if rows16 else contextlib.nullcontext
         self.iter_num = 0
         # HIP-event timing of the three contrastive-loss segments: only when a profiler asks for it (bench.py sets
         # profile_loss); a training run records no events (no stream bubbles, nothing accumulates)
@@ -283,6 +306,14 @@ class ArcoStep2D(LossScaleGuard):
         self.t_fwd_l = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
         self.t_fwd_u = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
         self.s_fwd_stats = graphs.GraphedForward(self.model, enabled=use_graphs)
+
+    def fm_rows_note(self):
+        """Which feature maps the heads read as f16 rows (for the log line of the f16 mode)."""
+        if not self.fm_keep_s:
+            return "--fm_rows f32: the heads read fp32 copies of all five feature maps"
+        names = ["f0", "f1", "f2", "f3", "f4"]
+        return ("--fm_rows f16: f16 rows of %s (student) and %s (teacher), no map cast in the logits-only passes"
+                % (", ".join(names[5 - self.fm_keep_s:]), ", ".join(names[5 - self.fm_keep_t:])))
 
     def q_rep(self, x):
         x = ops.conv(x, self.q_representation[0].weight)
@@ -336,7 +367,7 @@ class ArcoStep2D(LossScaleGuard):
             if self._t_stream is None:
                 self._t_stream = torch.cuda.Stream()
             self._t_stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._t_stream), torch.no_grad(), ops.bn_defer(0, 1):
+            with torch.cuda.stream(self._t_stream), torch.no_grad(), ops.bn_defer(0, 1), self._fm_none():
                 self.s_fwd_stats(cj2_l)
         # IMG_EARLY (cutout / cutmix): the IMAGE side of the mixing strategy and of the two batch_transform calls (:296-304) reads no
         # pseudo-label - the boxes, ColorJitter / blur parameters and AdvMorph fields are host / generator draws, labels pass through
@@ -358,7 +389,7 @@ class ArcoStep2D(LossScaleGuard):
                     zg = torch.zeros(u_mix.shape[:1] + u_mix.shape[2:], dtype=torch.float32, device=u_mix.device)
                     cj2_u = augment.batch_transform(u_mix, zl, zg, a.patch_size, (1.0, 1.0), True)[0]
                     u_aug = augment.batch_transform(u_mix, zl, zg, a.patch_size, (1.0, 1.0), True)[0]
-        with torch.no_grad():                                            # :284-286
+        with torch.no_grad(), self._fm_none():                           # :284-286 (reads the logits only)
             pred_u0, _, _ = self.t_fwd_u0(u_data)
             pseudo_logits, pseudo_labels = glue.softmax_max(pred_u0)
             if self.keep_debug:      # tests: the teacher's decisions before the mixing (cutout writes -1 into the labels in place)
@@ -394,26 +425,27 @@ class ArcoStep2D(LossScaleGuard):
                     self._t_stream = torch.cuda.Stream()
                 t_side = self._t_stream
                 t_side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(t_side), torch.no_grad(), ops.bn_groups(2):
+                with torch.cuda.stream(t_side), torch.no_grad(), ops.bn_groups(2), self._fm_t():
                     pred_t, _, fm_t = self.t_fwd_lu(lu)
-            with ops.bn_groups(2), ops.bn_defer(1):
+            with ops.bn_groups(2), ops.bn_defer(1), self._fm_s():
                 pred_all, _, fm_all = self.s_train_lu(lu)
             if t_side is not None:
                 torch.cuda.current_stream().wait_stream(t_side)
             nb_l = int(l_data.shape[0])
             pred_l, pred_u = ops.split_batch(pred_all, nb_l)    # (views; one gradient buffer for both halves in the backward)
         else:
-            with ops.bn_defer(0):                                        # running statistics: applied after l and cj2_l
+            with ops.bn_defer(0), self._fm_s():                          # running statistics: applied after l and cj2_l
                 pred_u, _, u_fm = self.s_train_u(u_aug)                  # :312 (needed first: entropy masks)
         with torch.no_grad():                                            # teacher params carry no grad (:158-160)
             if batched:
                 if not TEACHER_SIDE:
-                    with ops.bn_groups(2):
+                    with ops.bn_groups(2), self._fm_t():
                         pred_t, _, fm_t = self.t_fwd_lu(lu)              # :314-315 as one grouped pass
                 pred_l_t, pred_u_t = pred_t[:nb_l], pred_t[nb_l:]
             else:
-                pred_l_t, _, l_fm_t = self.t_fwd_l(l_data)               # :314
-                pred_u_t, _, u_fm_t = self.t_fwd_u(u_aug)                # :315
+                with self._fm_t():
+                    pred_l_t, _, l_fm_t = self.t_fwd_l(l_data)           # :314
+                    pred_u_t, _, u_fm_t = self.t_fwd_u(u_aug)            # :315
             alpha_t = 20 * (1 - epoch_num / max_epoch)                   # :342-393
             label_l = glue.label_onehot(l_label, C)
             label_u = glue.label_onehot(u_aug_label, C)
@@ -434,7 +466,8 @@ class ArcoStep2D(LossScaleGuard):
             ev[1].record()
         # ---- large GPU work queued while the host waits for the counters and samples
         if not batched:
-            pred_l, _, l_fm = self.s_train_l(l_data)                     # :310
+            with self._fm_s():
+                pred_l, _, l_fm = self.s_train_l(l_data)                 # :310
         with torch.no_grad():
             # images_cj2_l forward (:311): BN running statistics only - its FE/q_rep outputs (l_feature_map_2,
             # :319,326) are never read.  One graph launch (~1 ms of GPU work) queued BEFORE the host sync: work for
@@ -446,12 +479,13 @@ class ArcoStep2D(LossScaleGuard):
                 if self._t_stream is None:
                     self._t_stream = torch.cuda.Stream()
                 self._t_stream.wait_stream(torch.cuda.current_stream())     # behind the student pass: BN buffers in the reference's order
-                with torch.cuda.stream(self._t_stream):
+                with torch.cuda.stream(self._t_stream), self._fm_none():
                     self.s_fwd_stats(cj2_l)
                     ops.apply_deferred_bn()
                 self._stats_on_side = True
             else:
-                self.s_fwd_stats(cj2_l)
+                with self._fm_none():
+                    self.s_fwd_stats(cj2_l)
                 ops.apply_deferred_bn()                                  # the u pass's running-statistics update (:312)
             # FeatureExtractor is per-image -> run it once on the batch-concatenated maps (:321-322)
             if not batched:
@@ -523,7 +557,8 @@ class ArcoStep2D(LossScaleGuard):
                                    border_padding=False, random_mirror=True, random_scale=(0.8, 1.2), mode='affine',
                                    device=l_data.device)                 # :255-261 (draws one warp, like the reference)
             eq_mask, images_cj2, pred_all_d = eqv_in
-            tps_on_side = self._tps_side and self.s_train_tps.will_replay(images_cj2)
+            with self._fm_none():          # (the mode the warped pass is captured under: GraphedTrain replays under no other)
+                tps_on_side = self._tps_side and self.s_train_tps.will_replay(images_cj2)
             tps_early = tps_on_side and TEACHER_SIDE >= 4
             if tps_on_side and self._t_stream is None:
                 self._t_stream = torch.cuda.Stream()
@@ -539,12 +574,13 @@ class ArcoStep2D(LossScaleGuard):
                     mask_tps = self.tps(eq_mask, padding_mode='zeros')
                     pred_tps_org = self.tps(pred_all_d, padding_mode='zeros')
                 if tps_early:
-                    pred_tps = self.s_train_tps(images_tps)[0]           # :415
+                    with self._fm_none():                                # (reads the logits only)
+                        pred_tps = self.s_train_tps(images_tps)[0]       # :415
             if tps_early:
                 self.optimizer._g2_dirty = True
             elif tps_on_side:      # behind the statistics-only pass on that stream (running statistics: cj2_l, u, then this pass)
                 self._t_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(self._t_stream):
+                with torch.cuda.stream(self._t_stream), self._fm_none():
                     pred_tps = self.s_train_tps(images_tps)[0]
                 self._stats_on_side = False
                 self.optimizer._g2_dirty = True
@@ -552,7 +588,8 @@ class ArcoStep2D(LossScaleGuard):
                 if self._stats_on_side:    # the warped pass updates the same running statistics next
                     torch.cuda.current_stream().wait_stream(self._t_stream)
                     self._stats_on_side = False
-                pred_tps = self.s_train_tps(images_tps)[0]               # :415 one more student pass (one BN batch)
+                with self._fm_none():
+                    pred_tps = self.s_train_tps(images_tps)[0]           # :415 one more student pass (one BN batch)
                 loss_eqv = glue.eqv_loss(pred_tps, pred_tps_org, mask_tps)   # :419-423
         if enqueue_late:
             enqueue()
@@ -735,8 +772,8 @@ def train(args, snapshot_path):
             u_img = u_next['image'].to(dev, non_blocking=True)
         loss, reco = stepper.step(l_img, l_lab, u_img, it // iters_per_epoch, max_epoch)
         if rank == 0 and ops.ACT_HALF and (stepper.iter_num == 1 or stepper.iter_num % 50 == 0 or stepper.iter_num == args.max_iterations):
-            logging.info('iteration %d : --act_dtype f16, loss scale %g, %d overflowed step(s) so far'
-                         % (stepper.iter_num, ops.LOSS_SCALE, stepper.overflow_steps))
+            logging.info('iteration %d : --act_dtype f16, loss scale %g, %d overflowed step(s) so far; %s'
+                         % (stepper.iter_num, ops.LOSS_SCALE, stepper.overflow_steps, stepper.fm_rows_note()))
         if rank == 0:
             if "loss_q" in stepper.last_terms:                          # --revisit 1: the reference's logged total (:426,457)
                 logging.info('iteration %d : loss : %f, reco_loss: %f' % (stepper.iter_num, loss.item(), reco.item()))

@@ -274,6 +274,13 @@ int arco_lerp4_cat_rows(const float* V, long ldv, int Clo, const float* lylx, co
                         const int64_t* pix, long n, float* X, long ldx, void* stream);
 int arco_lerp4_cat_rows_bwd(const float* dX, long ldx, int Clo, const float* lylx, const int64_t* pix, long n, float* dV,
                             long ldv, float* dhi, long ldhi, int Chi, void* stream);
+/* ... with the map `hi` stored as f16 (f16 activation storage of the U-Net, train_arco_2d --fm_rows f16): ldhi in f16 elements,
+ * Chi % 4 == 0, ldhi >= Chi; lo / V and X fp32.  The f16 values are widened exactly, so X equals what the fp32 entry point
+ * returns on the upcast map bit for bit.  The adjoints keep fp32 targets (arco_cast_rows_f2h rounds the touched rows once).  */
+int arco_gather_upcat_rows_h(const float* lo, long ldlo, int Clo, int Hi, int Wi, const void* hi, long ldhi, int Chi,
+                             int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream);
+int arco_lerp4_cat_rows_h(const float* V, long ldv, int Clo, const float* lylx, const void* hi, long ldhi, int Chi,
+                          const int64_t* pix, long n, float* X, long ldx, void* stream);
 /* V-Net k2s2 (transposed) convs as GEMMs over packed 2x2x2 blocks (vnetWithArgs.py:67-118); trilinear
  * align_corners resize of FeatureExtractor_3d (model_3D.py:46-58)                                          */
 int arco_s2d3(float* V, long ldv, int NV, int X2, int Y2, int Z2, int C, float* P, long ldp, int dir, void* stream);
