@@ -480,6 +480,14 @@ def use_half(x, taps, ci):
         or (_OPEN_HALF_2D and taps == 9 and ci <= 4 and x.dim() == 4)
 
 
+def _check_open_layer(half, xr, taps, d3, k, n):
+    """The 3x3 layer that opens the 2-D f16 region (fp32 image in, f16 out) exists for <= 4 -> 16 channels: its weight-gradient
+    kernel reads 16 channels of the f16 gradient.  Anything else is refused here, before a pack or a kernel is launched, so that
+    a forward that succeeds is never followed by a backward that cannot run."""
+    if half and taps == 9 and d3 == 1 and not _is_half(xr) and (k > 4 or n != 16):
+        raise RuntimeError(f"arco_amd: f16 activation storage opens at a 3x3 layer of <= 4 -> 16 channels, got {k} -> {n}")
+
+
 def _half_pack(half, taps, ci):
     """Does an f16-storage convolution read the f16 weight pack?  Not the layers that open the region: they read an fp32 input
     (the V-Net's one-channel volume, the U-Net's image of <= 4 channels) with the fp32 pack."""
@@ -516,8 +524,7 @@ def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=
             raise RuntimeError("arco_amd: f16 activation storage has no consumer-side activation (ops.conv_block returns None)")
         mma = 4
         image_h = taps == 9 and d3 == 1 and not _is_half(xr)
-        if image_h and (k > 4 or n > 16 or n % 4):
-            raise RuntimeError(f"arco_amd: f16 activation storage opens at a 3x3 layer of <= 4 -> 16 channels, got {k} -> {n}")
+        _check_open_layer(half, xr, taps, d3, k, n)
     elif HEAD_MMA and taps == 1 and pro is None:
         mma = 2 if grad else HEAD_MMA                     # (wp is the fp32 pack: the operands are rounded in registers)
     elif CONV_MMA == 3:
@@ -785,6 +792,7 @@ class ConvFn(torch.autograd.Function):
         xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
         co = int(weight.shape[0])
         half = use_half(x, taps, ci)
+        _check_open_layer(half, xr, taps, d3, ci, co)
         wp = pack_weight(weight, taps, 0, half=_half_pack(half, taps, ci))
         if isinstance(residual, torch.Tensor):              # y = conv(x) + R  (R: any tensor of y's shape)
             rr, ldr = rows_view(residual)
@@ -883,6 +891,7 @@ class ConvBnActFn(torch.autograd.Function):
         co = int(weight.shape[0])
         m = nv * d3 * h * w
         half = use_half(x, taps, ci)
+        _check_open_layer(half, xr, taps, d3, ci, co)
         wp = pack_weight(weight, taps, 0, half=_half_pack(half, taps, ci))
         G = BN_GROUPS
         if G > 1 and nv % G != 0:
