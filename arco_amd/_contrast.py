@@ -365,7 +365,7 @@ def contrast_enqueue(pl, rep_teacher, memobank, queue_prtlis, queue_size, _trace
                    L.ptr(keys), D)
             key_rows.append(keys)
     else:
-        # lazy teacher (arco_amd.head.LazyTeacher2D / LazyTeacher3D): only the key rows that can survive the truncation
+        # lazy teacher (arco_amd.head.LazyTeacher): only the key rows that can survive the truncation
         pix = torch.cat([pl.lists[C + c][int(pl.n_neg[c]) - takes[c]:int(pl.n_neg[c])] for c in range(C)]).to(torch.int64)
         allk = lazy_teacher.rows(pix) if int(pix.shape[0]) > 0 else torch.empty((0, D), dtype=torch.float32, device=dev)
         key_rows, off = [], 0

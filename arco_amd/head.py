@@ -13,6 +13,7 @@ accumulation); the backward scatters dX4 rows back into x3p / f4 and the weight 
 GEMMs over the anchor rows only.  This removes ~3.3 TFLOP/step of dense fp32 GEMM work at
 BASELINE config 2 without changing any result.
 """
+import math
 import os
 
 import torch
@@ -60,167 +61,11 @@ def _fm_grad_buffer(half, ptr, shape, dev):
     return buf, done
 
 
-class LazyHeadFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x3p, f4, w4, w1, w2, pix):
-        lo, ldlo = rows_view(x3p)
-        hi, ldhi = rows_view(f4)
-        nb, clo, hi_h, hi_w = int(x3p.shape[0]), int(x3p.shape[1]), int(x3p.shape[2]), int(x3p.shape[3])
-        chi, ho, wo = int(f4.shape[1]), int(f4.shape[2]), int(f4.shape[3])
-        n = int(pix.shape[0])
-        X = torch.empty((n, clo + chi), dtype=torch.float32, device=x3p.device)
-        L.call(_h("arco_gather_upcat_rows", hi), L.ptr(lo), ldlo, clo, hi_h, hi_w, L.ptr(hi), ldhi, chi, ho, wo, L.ptr(pix), n,
-               L.ptr(X), clo + chi)
-        h0 = _gemm(X, w4)
-        h1 = _gemm(h0, w1)
-        a = _gemm(h1, w2)
-        ctx.save_for_backward(X, h0, h1, w4, w1, w2, pix)
-        ctx.geom = (nb, clo, hi_h, hi_w, chi, ho, wo)
-        ctx.fptrs = (f4.data_ptr(),)
-        ctx.fhalf = (f4.dtype == torch.float16,)      # ops.fm_rows_half: map consumed as stored
-        return a
-
-    @staticmethod
-    def backward(ctx, da):
-        X, h0, h1, w4, w1, w2, pix = ctx.saved_tensors
-        nb, clo, hi_h, hi_w, chi, ho, wo = ctx.geom
-        da = da.contiguous()
-        dw2 = _wgrad(da, h1, w2)
-        dh1 = _gemm_t(da, w2)
-        dw1 = _wgrad(dh1, h0, w1)
-        dh0 = _gemm_t(dh1, w1)
-        dw4 = _wgrad(dh0, X, w4)
-        dX = _gemm_t(dh0, w4)
-        n = int(pix.shape[0])
-        dlo = torch.zeros((nb, hi_h, hi_w, clo), dtype=torch.float32, device=da.device)
-        dhi, done = _fm_grad_buffer(ctx.fhalf[0], ctx.fptrs[0], (nb, chi, ho, wo), da.device)
-        _scatter_upcat2d(dX, clo + chi, pix, n, dlo, clo, hi_h, hi_w, dhi, chi, ho, wo)
-        dhi = done(pix, n)
-        return dlo.permute(0, 3, 1, 2), dhi.permute(0, 3, 1, 2), dw4, dw1, dw2, None
-
-
-def lazy_head(x3p, f4, fea4_weight, q1_weight, q2_weight, pix):
-    """Anchor rows of q_representation(FeatureExtractor(...)) at high-res pixel ids `pix`."""
-    return LazyHeadFn.apply(x3p, f4, fea4_weight, q1_weight, q2_weight, pix)
-
-
-def _rows2d_forward(x2p, f3, f4, w3, w4, pix):
-    """Two-level row path: X3 = cat(bilinear(x2p), f3) on the 4 low-res neighbours of each anchor, X3p = fea3(X3)+X3,
-    X4 = cat(4-way lerp of X3p, f4[pix]); returns (X3, X4, nb4, lylx, fea4(X4))."""
-    dev = x2p.device
-    n = int(pix.shape[0])
-    nb, c2, h2, w2_ = (int(v) for v in x2p.shape)
-    c3, h3, w3_ = int(f3.shape[1]), int(f3.shape[2]), int(f3.shape[3])
-    c4, h4, w4_ = int(f4.shape[1]), int(f4.shape[2]), int(f4.shape[3])
-    lo2, ld2 = rows_view(x2p)
-    r3, ld3 = rows_view(f3)
-    r4, ld4 = rows_view(f4)
-    nb4 = torch.empty(4 * n, dtype=torch.int64, device=dev)
-    lylx = torch.empty(2 * n, dtype=torch.float32, device=dev)
-    L.call("arco_up_neighbors", L.ptr(pix), n, h3, w3_, h4, w4_, L.ptr(nb4), L.ptr(lylx))
-    k3 = c2 + c3
-    X3 = torch.empty((4 * n, k3), dtype=torch.float32, device=dev)
-    L.call(_h("arco_gather_upcat_rows", r3), L.ptr(lo2), ld2, c2, h2, w2_, L.ptr(r3), ld3, c3, h3, w3_, L.ptr(nb4), 4 * n,
-           L.ptr(X3), k3)
-    y3, _ = ops.conv_raw(X3, k3, k3, ops.pack_weight(w3, 1, 0), k3, 1, 1, 4 * n, 1, residual=X3, ld_res=k3)
-    X3p = y3.permute(0, 2, 3, 1).reshape(4 * n, k3)                     # fea3(x)+x rows
-    k4 = k3 + c4
-    X4 = torch.empty((n, k4), dtype=torch.float32, device=dev)
-    L.call(_h("arco_lerp4_cat_rows", r4), L.ptr(X3p), k3, k3, L.ptr(lylx), L.ptr(r4), ld4, c4, L.ptr(pix), n, L.ptr(X4), k4)
-    return X3, X4, nb4, lylx, _gemm(X4, w4)
-
-
-class LazyHead2Fn(torch.autograd.Function):
-    """Two-level row-sparse head: also fea3 (the 128x128 level) is evaluated only on the <= 4 low-res
-    neighbours of each anchor.  Inputs: x2p = fea2(x)+x [B,448,64,64] (dense), f3 [B,32,128,128],
-    f4 [B,16,256,256].  Rows are bit-identical to the dense modules (same lerp order, same K-order MFMA
-    accumulation); d loss/d x2p becomes dense again from the 64x64 level down."""
-
-    @staticmethod
-    def forward(ctx, x2p, f3, f4, w3, w4, w1, w2, pix):
-        nb, c2, h2, w2_ = (int(v) for v in x2p.shape)
-        c3, h3, w3_ = int(f3.shape[1]), int(f3.shape[2]), int(f3.shape[3])
-        c4, h4, w4_ = int(f4.shape[1]), int(f4.shape[2]), int(f4.shape[3])
-        X3, X4, nb4, lylx, h0 = _rows2d_forward(x2p, f3, f4, w3, w4, pix)
-        h1 = _gemm(h0, w1)
-        a = _gemm(h1, w2)
-        ctx.save_for_backward(X3, X4, h0, h1, w3, w4, w1, w2, pix, nb4, lylx)
-        ctx.geom = (nb, c2, h2, w2_, c3, h3, w3_, c4, h4, w4_)
-        ctx.fptrs = (f3.data_ptr(), f4.data_ptr())
-        ctx.fhalf = (f3.dtype == torch.float16, f4.dtype == torch.float16)      # ops.fm_rows_half: maps consumed as stored
-        return a
-
-    @staticmethod
-    def backward(ctx, da):
-        X3, X4, h0, h1, w3, w4, w1, w2, pix, nb4, lylx = ctx.saved_tensors
-        nb, c2, h2, w2_, c3, h3, w3_, c4, h4, w4_ = ctx.geom
-        dev = da.device
-        n = int(pix.shape[0])
-        k3 = c2 + c3
-        da = da.contiguous()
-        dw2 = _wgrad(da, h1, w2)
-        dh1 = _gemm_t(da, w2)
-        dw1 = _wgrad(dh1, h0, w1)
-        dh0 = _gemm_t(dh1, w1)
-        dw4 = _wgrad(dh0, X4, w4)
-        dX4 = _gemm_t(dh0, w4)
-        dX3p = torch.empty((4 * n, k3), dtype=torch.float32, device=dev)
-        df4, done4 = _fm_grad_buffer(ctx.fhalf[1], ctx.fptrs[1], (nb, c4, h4, w4_), dev)
-        _lerp4_cat_rows_bwd(dX4, k3 + c4, k3, lylx, pix, n, dX3p, df4, c4)
-        df4 = done4(pix, n)
-        dw3 = _wgrad(dX3p, X3, w3)
-        # d(fea3(x)+x)/dx: W3^T dy + dy  (residual fused in the dgrad GEMM epilogue)
-        y, _ = ops.conv_raw(dX3p, k3, k3, ops.pack_weight(w3, 1, 1), k3, 1, 1, 4 * n, 1, residual=dX3p, ld_res=k3)
-        dX3 = y.permute(0, 2, 3, 1).reshape(4 * n, k3)
-        dx2p = torch.zeros((nb, h2, w2_, c2), dtype=torch.float32, device=dev)
-        df3, done3 = _fm_grad_buffer(ctx.fhalf[0], ctx.fptrs[0], (nb, c3, h3, w3_), dev)
-        _scatter_upcat2d(dX3, k3, nb4, 4 * n, dx2p, c2, h2, w2_, df3, c3, h3, w3_)
-        df3 = done3(nb4, 4 * n)
-        return (dx2p.permute(0, 3, 1, 2), df3.permute(0, 3, 1, 2), df4.permute(0, 3, 1, 2), dw3, dw4, dw1, dw2, None)
-
-
-def lazy_head2(x2p, f3, f4, fea3_weight, fea4_weight, q1_weight, q2_weight, pix):
-    return LazyHead2Fn.apply(x2p, f3, f4, fea3_weight, fea4_weight, q1_weight, q2_weight, pix)
-
-
 def _fea_rows(X, w, mode):
     """fea_i(X) + X on rows (mode 0) / its data gradient W^T dY + dY (mode 1): the 1x1 conv with the residual in the GEMM epilogue."""
     k = int(X.shape[1])
     y, _ = ops.conv_raw(X, k, k, ops.pack_weight(w, 1, mode), k, 1, 1, int(X.shape[0]), 1, residual=X, ld_res=k)
     return y.permute(0, 2, 3, 1).reshape(int(X.shape[0]), k)
-
-
-def _rows3lvl_forward(x1p, f2, f3, f4, w2, w3, w4, pix):
-    """Three-level row path: the 4 neighbours at f3's resolution of every anchor, the 4 neighbours at f2's resolution of
-    each of those; X2 = cat(bilinear(x1p), f2) on the 16 n rows, X2p = fea2(X2)+X2, X3 = cat(4-way lerp of X2p, f3 rows),
-    X3p = fea3(X3)+X3, X4 = cat(4-way lerp of X3p, f4[pix]).  Returns (X2, X3, X4, nb4, nb16, lylx3, lylx4, fea4(X4))."""
-    dev = x1p.device
-    n = int(pix.shape[0])
-    nb, c1, h1, w1_ = (int(v) for v in x1p.shape)
-    c2, h2, w2_ = int(f2.shape[1]), int(f2.shape[2]), int(f2.shape[3])
-    c3, h3, w3_ = int(f3.shape[1]), int(f3.shape[2]), int(f3.shape[3])
-    c4, h4, w4_ = int(f4.shape[1]), int(f4.shape[2]), int(f4.shape[3])
-    lo1, ld1 = rows_view(x1p)
-    r2, ld2 = rows_view(f2)
-    r3, ld3 = rows_view(f3)
-    r4, ld4 = rows_view(f4)
-    nb4 = torch.empty(4 * n, dtype=torch.int64, device=dev)
-    lylx4 = torch.empty(2 * n, dtype=torch.float32, device=dev)
-    L.call("arco_up_neighbors", L.ptr(pix), n, h3, w3_, h4, w4_, L.ptr(nb4), L.ptr(lylx4))
-    nb16 = torch.empty(16 * n, dtype=torch.int64, device=dev)
-    lylx3 = torch.empty(8 * n, dtype=torch.float32, device=dev)
-    L.call("arco_up_neighbors", L.ptr(nb4), 4 * n, h2, w2_, h3, w3_, L.ptr(nb16), L.ptr(lylx3))
-    k2, k3, k4 = c1 + c2, c1 + c2 + c3, c1 + c2 + c3 + c4
-    X2 = torch.empty((16 * n, k2), dtype=torch.float32, device=dev)
-    L.call(_h("arco_gather_upcat_rows", r2), L.ptr(lo1), ld1, c1, h1, w1_, L.ptr(r2), ld2, c2, h2, w2_, L.ptr(nb16), 16 * n,
-           L.ptr(X2), k2)
-    X2p = _fea_rows(X2, w2, 0)
-    X3 = torch.empty((4 * n, k3), dtype=torch.float32, device=dev)
-    L.call(_h("arco_lerp4_cat_rows", r3), L.ptr(X2p), k2, k2, L.ptr(lylx3), L.ptr(r3), ld3, c3, L.ptr(nb4), 4 * n, L.ptr(X3), k3)
-    X3p = _fea_rows(X3, w3, 0)
-    X4 = torch.empty((n, k4), dtype=torch.float32, device=dev)
-    L.call(_h("arco_lerp4_cat_rows", r4), L.ptr(X3p), k3, k3, L.ptr(lylx4), L.ptr(r4), ld4, c4, L.ptr(pix), n, L.ptr(X4), k4)
-    return X2, X3, X4, nb4, nb16, lylx3, lylx4, _gemm(X4, w4)
 
 
 def _row_grad_buffer(ptr, shape, dev):
@@ -338,64 +183,238 @@ def _lerp4_cat_rows_bwd(dX, ldx, clo, lylx, pix, n, dV, dhi, chi):
         L.call("arco_lerp4_cat_rows_bwd", L.ptr(dX), ldx, clo, L.ptr(lylx), L.ptr(pix), n, L.ptr(dV), clo, L.ptr(dhi), chi, chi)
 
 
-class LazyHead3Fn(torch.autograd.Function):
-    """Three-level row-sparse head: fea2 (the 64 x 64 level), fea3 and fea4 are all evaluated only where the anchors need
-    them - the 4 neighbours at 128 x 128 of every anchor and the 4 neighbours at 64 x 64 of each of those (16 n rows of
-    448 channels instead of the 65 536 rows of the dense 64 x 64 map: ~1000 anchors per step).  Inputs: x1p =
-    fea1(x)+x [B,384,32,32] (dense), f2 [B,64,64,64], f3 [B,32,128,128], f4 [B,16,256,256].  Same kernels as the two-level
-    head, applied once more; d loss / d x1p becomes dense again from the 32 x 32 level down.  The dense fea2 GEMM
-    (65 536 x 448 x 64 + the upsampled 117 MB residual), its data and weight gradients and the 64 x 64 bilinear backward
-    leave the student path."""
+def _q_tail(X, w4, w1, w2):
+    """fea4, q_representation[0] and [1] on rows: (h0, h1, a)."""
+    h0 = _gemm(X, w4)
+    h1 = _gemm(h0, w1)
+    return h0, h1, _gemm(h1, w2)
+
+
+def _q_tail_bwd(da, X, h0, h1, w4, w1, w2):
+    """adjoint of _q_tail: (dX, dw4, dw1, dw2) - the weight gradients are GEMMs over the anchor rows only."""
+    da = da.contiguous()
+    dw2 = _wgrad(da, h1, w2)
+    dh1 = _gemm_t(da, w2)
+    dw1 = _wgrad(dh1, h0, w1)
+    dh0 = _gemm_t(dh1, w1)
+    dw4 = _wgrad(dh0, X, w4)
+    return _gemm_t(dh0, w4), dw4, dw1, dw2
+
+
+def _rows2d(lo, maps, feas, pix):
+    """The 2-D row path through L = len(maps) levels (maps and feas coarse to fine).  idx[L-1] = pix and idx[i-1] = the 4 neighbours at
+    maps[i-1]'s resolution of every row of idx[i] (4^(L-1-i) n rows at level i); Xs[0] = cat(bilinear(lo), maps[0]) on idx[0];
+    Xs[i] = cat(4-way lerp of fea_i(Xs[i-1])+Xs[i-1], maps[i][idx[i]]).  Returns (Xs, idx, lylx) as lists by level, lylx[i] being the
+    lerp coefficients into level i (lylx[0] is None); Xs[-1] is the input rows of fea4."""
+    dev = lo.device
+    nl = len(maps)
+    lo_r, ldlo = rows_view(lo)
+    rv = [rows_view(m) for m in maps]
+    idx, lylx = [None] * (nl - 1) + [pix], [None] * nl
+    for i in range(nl - 1, 0, -1):
+        m = int(idx[i].shape[0])
+        idx[i - 1] = torch.empty(4 * m, dtype=torch.int64, device=dev)
+        lylx[i] = torch.empty(2 * m, dtype=torch.float32, device=dev)
+        L.call("arco_up_neighbors", L.ptr(idx[i]), m, *maps[i - 1].shape[2:], *maps[i].shape[2:], L.ptr(idx[i - 1]), L.ptr(lylx[i]))
+    (r, ld), m = rv[0], int(idx[0].shape[0])
+    k = int(lo.shape[1]) + int(maps[0].shape[1])
+    X = torch.empty((m, k), dtype=torch.float32, device=dev)
+    L.call(_h("arco_gather_upcat_rows", r), L.ptr(lo_r), ldlo, *lo.shape[1:], L.ptr(r), ld, *maps[0].shape[1:], L.ptr(idx[0]), m,
+           L.ptr(X), k)
+    Xs = [X]
+    for i in range(1, nl):
+        (r, ld), m, c = rv[i], int(idx[i].shape[0]), int(maps[i].shape[1])
+        Xp = _fea_rows(X, feas[i - 1], 0)                     # fea_i(x)+x rows
+        X = torch.empty((m, k + c), dtype=torch.float32, device=dev)
+        L.call(_h("arco_lerp4_cat_rows", r), L.ptr(Xp), k, k, L.ptr(lylx[i]), L.ptr(r), ld, c, L.ptr(idx[i]), m, L.ptr(X), k + c)
+        Xs.append(X)
+        k += c
+    return Xs, idx, lylx
+
+
+class LazyHead2dFn(torch.autograd.Function):
+    """Row-sparse 2-D head over L = 1, 2 or 3 levels: fea_(5-L) .. fea3 and fea4 are evaluated only where the anchors need them - the 4
+    neighbours at the next coarser map of every anchor, the 4 neighbours one map further down of each of those, ...  Inputs (reached
+    through lazy_head2d): lo = the dense fea_(4-L)(x)+x and the L finest maps, e.g. L = 3: x1p = fea1(x)+x [B,384,32,32], f2 [B,64,64,64],
+    f3 [B,32,128,128], f4 [B,16,256,256] - 16 n rows of 448 channels instead of the 65 536 rows of the dense 64 x 64 map (~1000 anchors
+    per step): the dense fea2 GEMM (65 536 x 448 x 64 + the upsampled 117 MB residual), its data and weight gradients and the 64 x 64
+    bilinear backward leave the student path.  Rows are bit-identical to the dense modules (same lerp order, same K-order MFMA
+    accumulation); d loss / d lo becomes dense again from lo's level down."""
 
     @staticmethod
-    def forward(ctx, x1p, f2, f3, f4, w2, w3, w4, w1, wq2, pix):
-        X2, X3, X4, nb4, nb16, lylx3, lylx4, h0 = _rows3lvl_forward(x1p, f2, f3, f4, w2, w3, w4, pix)
-        hh = _gemm(h0, w1)
-        a = _gemm(hh, wq2)
-        ctx.save_for_backward(X2, X3, X4, h0, hh, w2, w3, w4, w1, wq2, pix, nb4, nb16, lylx3, lylx4)
-        ctx.fptrs = (f2.data_ptr(), f3.data_ptr(), f4.data_ptr())
-        ctx.fhalf = (f2.dtype == torch.float16, f3.dtype == torch.float16, f4.dtype == torch.float16)      # ops.fm_rows_half
-        ctx.geom = (int(x1p.shape[0]), int(x1p.shape[1]), int(x1p.shape[2]), int(x1p.shape[3]),
-                    int(f2.shape[1]), int(f2.shape[2]), int(f2.shape[3]), int(f3.shape[1]), int(f3.shape[2]), int(f3.shape[3]),
-                    int(f4.shape[1]), int(f4.shape[2]), int(f4.shape[3]))
+    def forward(ctx, lo, w1, w2, pix, *maps_feas):
+        nl = len(maps_feas) // 2
+        maps, feas = maps_feas[:nl], maps_feas[nl:]
+        Xs, idx, lylx = _rows2d(lo, maps, feas, pix)
+        h0, h1, a = _q_tail(Xs[-1], feas[-1], w1, w2)
+        ctx.save_for_backward(h0, h1, w1, w2, *Xs, *feas, *idx, *lylx)
+        ctx.shapes = (tuple(lo.shape),) + tuple(tuple(m.shape) for m in maps)
+        ctx.fptrs = tuple(m.data_ptr() for m in maps)
+        ctx.fhalf = tuple(m.dtype == torch.float16 for m in maps)      # ops.fm_rows_half: maps consumed as stored
         return a
 
     @staticmethod
     def backward(ctx, da):
-        X2, X3, X4, h0, hh, w2, w3, w4, w1, wq2, pix, nb4, nb16, lylx3, lylx4 = ctx.saved_tensors
-        nb, c1, h1, w1_, c2, h2, w2_, c3, h3, w3_, c4, h4, w4_ = ctx.geom
+        nl = len(ctx.fptrs)
+        h0, h1, w1, w2 = ctx.saved_tensors[:4]
+        Xs, feas, idx, lylx = (ctx.saved_tensors[4 + j * nl:4 + (j + 1) * nl] for j in range(4))
+        (nb, clo, hlo, wlo), ms = ctx.shapes[0], ctx.shapes[1:]
         dev = da.device
-        n = int(pix.shape[0])
-        k2, k3 = c1 + c2, c1 + c2 + c3
-        da = da.contiguous()
-        dwq2 = _wgrad(da, hh, wq2)
-        dhh = _gemm_t(da, wq2)
-        dw1 = _wgrad(dhh, h0, w1)
-        dh0 = _gemm_t(dhh, w1)
-        dw4 = _wgrad(dh0, X4, w4)
-        dX4 = _gemm_t(dh0, w4)
-        dX3p = torch.empty((4 * n, k3), dtype=torch.float32, device=dev)
-        df4, done4 = _fm_grad_buffer(ctx.fhalf[2], ctx.fptrs[2], (nb, c4, h4, w4_), dev)
-        _lerp4_cat_rows_bwd(dX4, k3 + c4, k3, lylx4, pix, n, dX3p, df4, c4)
-        df4 = done4(pix, n)
-        dw3 = _wgrad(dX3p, X3, w3)
-        dX3 = _fea_rows(dX3p, w3, 1)
-        dX2p = torch.empty((16 * n, k2), dtype=torch.float32, device=dev)
-        df3, done3 = _fm_grad_buffer(ctx.fhalf[1], ctx.fptrs[1], (nb, c3, h3, w3_), dev)
-        _lerp4_cat_rows_bwd(dX3, k3, k2, lylx3, nb4, 4 * n, dX2p, df3, c3)
-        df3 = done3(nb4, 4 * n)
-        dw2 = _wgrad(dX2p, X2, w2)
-        dX2 = _fea_rows(dX2p, w2, 1)
-        dx1p = torch.zeros((nb, h1, w1_, c1), dtype=torch.float32, device=dev)
-        df2, done2 = _fm_grad_buffer(ctx.fhalf[0], ctx.fptrs[0], (nb, c2, h2, w2_), dev)
-        _scatter_upcat2d(dX2, k2, nb16, 16 * n, dx1p, c1, h1, w1_, df2, c2, h2, w2_)
-        df2 = done2(nb16, 16 * n)
-        return (dx1p.permute(0, 3, 1, 2), df2.permute(0, 3, 1, 2), df3.permute(0, 3, 1, 2), df4.permute(0, 3, 1, 2),
-                dw2, dw3, dw4, dw1, dwq2, None)
+        dX, dw4, dw1, dw2 = _q_tail_bwd(da, Xs[-1], h0, h1, feas[-1], w1, w2)
+        dmaps, dws = [None] * nl, [None] * (nl - 1) + [dw4]
+        for i in range(nl - 1, 0, -1):
+            m, k, c = int(idx[i].shape[0]), int(Xs[i - 1].shape[1]), ms[i][1]
+            dXp = torch.empty((4 * m, k), dtype=torch.float32, device=dev)
+            buf, done = _fm_grad_buffer(ctx.fhalf[i], ctx.fptrs[i], ms[i], dev)
+            _lerp4_cat_rows_bwd(dX, k + c, k, lylx[i], idx[i], m, dXp, buf, c)
+            dmaps[i] = done(idx[i], m)
+            dws[i - 1] = _wgrad(dXp, Xs[i - 1], feas[i - 1])
+            dX = _fea_rows(dXp, feas[i - 1], 1)     # d(fea_i(x)+x)/dx: W^T dy + dy  (residual fused in the dgrad GEMM epilogue)
+        m, (c, h, w) = int(idx[0].shape[0]), ms[0][1:]
+        dlo = torch.zeros((nb, hlo, wlo, clo), dtype=torch.float32, device=dev)
+        buf, done = _fm_grad_buffer(ctx.fhalf[0], ctx.fptrs[0], ms[0], dev)
+        _scatter_upcat2d(dX, clo + c, idx[0], m, dlo, clo, hlo, wlo, buf, c, h, w)
+        dmaps[0] = done(idx[0], m)
+        return (dlo.permute(0, 3, 1, 2), dw1, dw2, None, *(d.permute(0, 3, 1, 2) for d in dmaps), *dws)
 
 
-def lazy_head3(x1p, f2, f3, f4, fea2_weight, fea3_weight, fea4_weight, q1_weight, q2_weight, pix):
-    return LazyHead3Fn.apply(x1p, f2, f3, f4, fea2_weight, fea3_weight, fea4_weight, q1_weight, q2_weight, pix)
+def lazy_head2d(lo, maps, fea_weights, q1_weight, q2_weight, pix):
+    """Anchor rows of q_representation(FeatureExtractor(...)) at high-res pixel ids `pix`: lo = the dense low-resolution input
+    fea_(4-L)(x)+x, maps = the L = 1, 2 or 3 finest feature maps coarse to fine, fea_weights = the L fea weights above lo (the last
+    being fea4) - FeatureExtractor.forward_lowres / forward_lowres2 / forward_lowres1 return (lo, *maps)."""
+    return LazyHead2dFn.apply(lo, q1_weight, q2_weight, pix, *maps, *fea_weights)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The 3-D heads.  The 3-D pyramid is not the 2-D one: the two finest maps f3, f4 share a resolution, so everything above the
+# 56x56x40 level is per-voxel (fea3, the identity resize, fea4, q_rep) and the join with f4 is a plain row gather.  Two levels
+# (maps = f3, f4): one trilinear gather from the dense x2p = fea2(x)+x suffices.  Three levels (maps = f2, f3, f4; round 6), the
+# 56x56x40 level lazy too: a sampled voxel needs exactly its EIGHT trilinear corners of x2p = fea2(cat(up(x1p), f2)) + cat(...):
+# 8 n rows of 224 channels instead of the dense 501 760-row map (450 MB at the LA size: the step's longest GEMM launch writes it,
+# its prototype sums, its resize adjoint, its data and weight gradients read it - for ~1 % of its rows).
+# x1p = fea1(...)+... [B,192,28,28,20] stays dense.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _rows3d(lo, maps, feas, pix):
+    """The 3-D row path.  Two levels: X3 = cat(trilinear(lo)[pix], f3[pix]).  Three levels: the corner rows idx8 (at f2's resolution,
+    weights w8) of every sampled voxel, X2 = cat(trilinear(lo), f2) on them, X3 = cat(trilinear blend of the eight rows of
+    fea2(X2)+X2, f3[pix]).  Both: X4 = cat(fea3(X3)+X3, f4[pix]).  Returns ([X2,] X3, X4), idx8, w8 (None with two levels)."""
+    dev = pix.device
+    n = int(pix.shape[0])
+    three = len(maps) == 3
+    lo_r, ldlo = rows_view(lo)
+    rv = [rows_view(m) for m in maps]
+    at, idx8, w8 = pix, None, None
+    if three:
+        at = idx8 = torch.empty(8 * n, dtype=torch.int64, device=dev)
+        w8 = torch.empty(8 * n, dtype=torch.float32, device=dev)
+        L.call("arco_corner_rows3d", L.ptr(pix), n, *maps[0].shape[2:], *maps[1].shape[2:], L.ptr(idx8), L.ptr(w8))
+    (r, ld), m = rv[0], int(at.shape[0])
+    k = int(lo.shape[1]) + int(maps[0].shape[1])
+    X = torch.empty((m, k), dtype=torch.float32, device=dev)
+    L.call(_h("arco_gather_upcat_rows3d", r), L.ptr(lo_r), ldlo, *lo.shape[1:], L.ptr(r), ld, *maps[0].shape[1:], L.ptr(at), m,
+           L.ptr(X), k)
+    Xs = [X]
+    if three:
+        (r, ld), c = rv[1], int(maps[1].shape[1])
+        Xp = _fea_rows(X, feas[0], 0)
+        X = torch.empty((n, k + c), dtype=torch.float32, device=dev)
+        L.call(_h("arco_lerp8_cat_rows3d", r), L.ptr(Xp), k, k, *maps[0].shape[2:], L.ptr(r), ld, *maps[1].shape[1:], L.ptr(pix), n,
+               L.ptr(X), k + c)
+        Xs.append(X)
+        k += c
+    (r, ld), c = rv[-1], int(maps[-1].shape[1])
+    X4 = torch.empty((n, k + c), dtype=torch.float32, device=dev)
+    X4[:, :k] = _fea_rows(X, feas[-2], 0)
+    L.call(_h("arco_gather_rows", r), L.ptr(r), ld, c, None, L.ptr(pix), None, 0, n, L.ptr(X4[:, k:]), k + c)
+    return Xs + [X4], idx8, w8
+
+
+def _scatter_map_rows(src, ld_src, C, idx, n_e, half, ptr, shape, dev):
+    """The gradient of a 3-D feature map read as plain rows, dmap[idx[e]] += src[e] in the map's row-gradient buffer (order-independent
+    by default, DET_SCATTER); returns the gradient to hand back, channels-last."""
+    buf, done = _fm_grad_buffer(half, ptr, shape, dev)
+    if DET_SCATTER:
+        _det_scatter_rows(src, ld_src, C, 1, idx, None, n_e, buf, C)
+    else:
+        L.call("arco_scatter_add_rows", L.ptr(src), ld_src, C, None, L.ptr(idx), n_e, None, 1.0, L.ptr(buf), C)
+    return done(idx, n_e)
+
+
+def _det_scatter_corners3d(dX, ldx, clo, at, m, sp_lo, sp_hi, dlo):
+    """order-independent adjoint of the trilinear part of arco_gather_upcat_rows3d: dlo += the eight weighted corners of dX[:, :clo]"""
+    idx = torch.empty(8 * m, dtype=torch.int64, device=dX.device)
+    w = torch.empty(8 * m, dtype=torch.float32, device=dX.device)
+    L.call("arco_corner_rows3d", L.ptr(at), m, *sp_lo, *sp_hi, L.ptr(idx), L.ptr(w))
+    _det_scatter_rows(dX, ldx, clo, 8, idx, w, 8 * m, dlo, clo)
+
+
+class LazyHead3dFn(torch.autograd.Function):
+    """Row-sparse student head of the 3-D step: q_representation(FeatureExtractor_3d(...)) rows at the sampled voxels only
+    (model_3D.py:46-58, train_arco_3d.py:289-296).  Two levels: lo = x2p = fea2(x)+x (dense), maps f3, f4.  Three levels, fea2
+    evaluated on rows too: lo = x1p = fea1(.)+. [B,192,28,28,20] (dense), maps f2 [B,32,56,56,40], f3, f4 [B,16,112,112,80]; the
+    gradient becomes dense again from the 28x28x20 level down (48 MB).  The maps' gradients are row scatters (order-independent by
+    default, DET_SCATTER)."""
+
+    @staticmethod
+    def forward(ctx, lo, w1, w2, pix, *maps_feas):
+        nl = len(maps_feas) // 2
+        maps, feas = maps_feas[:nl], maps_feas[nl:]
+        Xs, idx8, w8 = _rows3d(lo, maps, feas, pix)
+        h0, h1, a = _q_tail(Xs[-1], feas[-1], w1, w2)
+        ctx.save_for_backward(h0, h1, w1, w2, pix, idx8, w8, *Xs, *feas)
+        ctx.shapes = (tuple(lo.shape),) + tuple(tuple(m.shape) for m in maps)
+        ctx.fptrs = tuple(m.data_ptr() for m in maps)
+        ctx.fhalf = tuple(m.dtype == torch.float16 for m in maps)      # ops.fm_rows_half: maps consumed as stored
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        nl = len(ctx.fptrs)
+        h0, h1, w1, w2, pix, idx8, w8 = ctx.saved_tensors[:7]
+        Xs, feas = ctx.saved_tensors[7:7 + nl], ctx.saved_tensors[7 + nl:]
+        sl, ms = ctx.shapes[0], ctx.shapes[1:]
+        dev = da.device
+        n, clo = int(pix.shape[0]), sl[1]
+        k3, c3, c4 = int(Xs[-2].shape[1]), ms[-2][1], ms[-1][1]
+
+        def dmap(i, src, ld_src, idx, n_e):
+            return _scatter_map_rows(src, ld_src, ms[i][1], idx, n_e, ctx.fhalf[i], ctx.fptrs[i], ms[i], dev)
+        dX4, dw4, dw1, dw2 = _q_tail_bwd(da, Xs[-1], h0, h1, feas[-1], w1, w2)
+        dX3p = dX4[:, :k3].contiguous()
+        df4 = dmap(nl - 1, dX4[:, k3:], k3 + c4, pix, n)
+        dw3 = _wgrad(dX3p, Xs[-2], feas[-2])
+        dX3 = _fea_rows(dX3p, feas[-2], 1)
+        dlo = torch.zeros((sl[0], *sl[2:], clo), dtype=torch.float32, device=dev)
+        if nl == 2:
+            df3, done = _fm_grad_buffer(ctx.fhalf[0], ctx.fptrs[0], ms[0], dev)
+            if DET_SCATTER:
+                _det_scatter_corners3d(dX3, k3, clo, pix, n, sl[2:], ms[0][2:], dlo)
+                _det_scatter_rows(dX3[:, clo:], k3, c3, 1, pix, None, n, df3, c3)
+            else:
+                L.call("arco_scatter_upcat_rows3d", L.ptr(dX3), k3, L.ptr(pix), n, L.ptr(dlo), clo, clo, *sl[2:],
+                       L.ptr(df3), c3, c3, *ms[0][2:])
+            df3 = done(pix, n)
+            return (dlo.movedim(-1, 1), dw1, dw2, None, df3.movedim(-1, 1), df4.movedim(-1, 1), dw3, dw4)
+        k2, c2 = int(Xs[0].shape[1]), ms[0][1]
+        df3 = dmap(1, dX3[:, k2:], k3, pix, n)
+        dX2p = torch.empty((8 * n, k2), dtype=torch.float32, device=dev)
+        L.call("arco_lerp8_rows3d_bwd", L.ptr(dX3), k3, k2, L.ptr(w8), n, L.ptr(dX2p), k2)
+        dw2f = _wgrad(dX2p, Xs[0], feas[0])
+        dX2 = _fea_rows(dX2p, feas[0], 1)
+        df2 = dmap(0, dX2[:, clo:], k2, idx8, 8 * n)
+        if DET_SCATTER:
+            _det_scatter_corners3d(dX2, k2, clo, idx8, 8 * n, sl[2:], ms[0][2:], dlo)
+        else:       # (the fp32-atomic adjoint of the gather: lo part only - dhi = a scratch row sink of the right shape)
+            sink = torch.zeros((ms[0][0], *ms[0][2:], c2), dtype=torch.float32, device=dev)
+            L.call("arco_scatter_upcat_rows3d", L.ptr(dX2), k2, L.ptr(idx8), 8 * n, L.ptr(dlo), clo, clo, *sl[2:],
+                   L.ptr(sink), c2, c2, *ms[0][2:])
+        return (dlo.movedim(-1, 1), dw1, dw2, None, df2.movedim(-1, 1), df3.movedim(-1, 1), df4.movedim(-1, 1), dw2f, dw3, dw4)
+
+
+def lazy_head3d(lo, maps, fea_weights, q1_weight, q2_weight, pix):
+    """Rows of q_representation(FeatureExtractor_3d(...)) at the sampled voxels `pix`: (lo, maps) = what forward_lowres2 (x2p, f3, f4)
+    or forward_lowres1 (x1p, f2, f3, f4) returns, fea_weights = the fea weights above lo (the last being fea4)."""
+    return LazyHead3dFn.apply(lo, q1_weight, q2_weight, pix, *maps, *fea_weights)
 
 
 def _class_weights(pl):
@@ -412,391 +431,55 @@ def _wsum(rows, ld, wt, ldw, n_rows, C, D, totals, out, ldo):
     L.call(fn, L.ptr(rows), ld, L.ptr(wt), ldw, n_rows, C, D, L.ptr(totals), L.ptr(ws), L.ptr(out), ldo)
 
 
-class LazyTeacher2D:
-    """Teacher side of the 2-D step without the dense 496-channel tensor: x3p = fea3(x)+x [B,480,128,128],
-    f4 [B,16,256,256], w4 = fea4 weight (model_2D.py:51-53)."""
+class LazyTeacher:
+    """Teacher side of the 2-D and 3-D steps without the dense 496-channel tensor, for (lo, maps, fea weights) as the student heads of
+    either rank take them (model_2D.py:51-53, model_3D.py:46-58).  Every map is linear in the feature maps, so
+        prototype_c = W4 . cat((W3+I) . cat((W2+I) . cat(S(lo; w''), S(f2; w')), S(f3; w)), S(f4; w))         (three levels)
+    with S(t; w) = the class-weighted row sums (class means) of t and the class mask w pushed through the resize adjoint once per change
+    of resolution below the finest map (2-D, three levels: 256^2 -> 128^2 -> 64^2 -> 32^2, the weighted row sums reading 66 MB
+    instead of the dense 117 MB fea2 output, which is not built at all; 3-D: f3 shares f4's resolution and its mask).  Key rows are
+    evaluated at the key pixels only, through the student's row path."""
 
-    def __init__(self, x3p, f4, w4):
-        self.x3p, self.f4, self.w4 = x3p, f4, w4
-
-    @torch.no_grad()
-    def prototypes(self, pl):
-        lo, ldlo = rows_view(self.x3p)
-        hi, ldhi = rows_view(self.f4)
-        nb, clo, hi_h, hi_w = (int(v) for v in self.x3p.shape)
-        chi, ho, wo = int(self.f4.shape[1]), int(self.f4.shape[2]), int(self.f4.shape[3])
-        C, K, D = pl.C, clo + chi, int(self.w4.shape[0])
-        wm, Cp = _class_weights(pl)
-        n_lo = nb * hi_h * hi_w
-        wlo = torch.empty((n_lo, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_bilinear_bwd", L.ptr(wm), Cp, nb, hi_h, hi_w, Cp, ho, wo, L.ptr(wlo), Cp, 0)
-        S = torch.zeros((_ceil(C, 16), K), dtype=torch.float32, device=pl.dev)
-        _wsum(lo, ldlo, wlo, Cp, n_lo, C, clo, pl.totals, S, K)
-        _wsum(hi, ldhi, wm, Cp, pl.n_pix, C, chi, pl.totals, S[:, clo:], K)
-        return _gemm(S, self.w4)[:C].contiguous()
-
-    @torch.no_grad()
-    def rows(self, pix):
-        lo, ldlo = rows_view(self.x3p)
-        hi, ldhi = rows_view(self.f4)
-        nb, clo, hi_h, hi_w = (int(v) for v in self.x3p.shape)
-        chi, ho, wo = int(self.f4.shape[1]), int(self.f4.shape[2]), int(self.f4.shape[3])
-        n = int(pix.shape[0])
-        X = torch.empty((n, clo + chi), dtype=torch.float32, device=pix.device)
-        L.call(_h("arco_gather_upcat_rows", hi), L.ptr(lo), ldlo, clo, hi_h, hi_w, L.ptr(hi), ldhi, chi, ho, wo, L.ptr(pix), n,
-               L.ptr(X), clo + chi)
-        return _gemm(X, self.w4)
-
-
-def _rows3d_forward(x2p, f3, f4, w3, w4, pix):
-    """X3 = cat(trilinear(x2p)[pix], f3[pix]); X3p = fea3(X3)+X3; X4 = cat(X3p, f4[pix]); returns (X3, X4, fea4(X4))."""
-    lo, ldlo = rows_view(x2p)
-    r3, ld3 = rows_view(f3)
-    r4, ld4 = rows_view(f4)
-    nb, c2, d2, h2, w2_ = (int(v) for v in x2p.shape)
-    c3, d3, h3, w3_ = (int(v) for v in f3.shape[1:])
-    c4 = int(f4.shape[1])
-    n = int(pix.shape[0])
-    k3 = c2 + c3
-    X3 = torch.empty((n, k3), dtype=torch.float32, device=pix.device)
-    L.call("arco_gather_upcat_rows3d_h" if r3.dtype == torch.float16 else "arco_gather_upcat_rows3d",
-           L.ptr(lo), ldlo, c2, d2, h2, w2_, L.ptr(r3), ld3, c3, d3, h3, w3_, L.ptr(pix), n, L.ptr(X3), k3)
-    y3, _ = ops.conv_raw(X3, k3, k3, ops.pack_weight(w3, 1, 0), k3, 1, 1, n, 1, residual=X3, ld_res=k3)
-    X4 = torch.empty((n, k3 + c4), dtype=torch.float32, device=pix.device)
-    X4[:, :k3] = y3.permute(0, 2, 3, 1).reshape(n, k3)
-    L.call("arco_gather_rows_h" if r4.dtype == torch.float16 else "arco_gather_rows",
-           L.ptr(r4), ld4, c4, None, L.ptr(pix), None, 0, n, L.ptr(X4[:, k3:]), k3 + c4)
-    return X3, X4, _gemm(X4, w4)
-
-
-class LazyHead3dFn(torch.autograd.Function):
-    """Row-sparse student head of the 3-D step: q_representation(FeatureExtractor_3d(...)) rows at the sampled
-    voxels only.  Everything above the 56x56x40 level is per-voxel (fea3, the identity resize, fea4, q_rep),
-    so one trilinear gather from x2p = fea2(x)+x suffices (model_3D.py:46-58, train_arco_3d.py:289-296)."""
-
-    @staticmethod
-    def forward(ctx, x2p, f3, f4, w3, w4, w1, w2, pix):
-        X3, X4, h0 = _rows3d_forward(x2p, f3, f4, w3, w4, pix)
-        h1 = _gemm(h0, w1)
-        a = _gemm(h1, w2)
-        ctx.save_for_backward(X3, X4, h0, h1, w3, w4, w1, w2, pix)
-        ctx.shapes = (tuple(x2p.shape), tuple(f3.shape), tuple(f4.shape))
-        ctx.fptrs = (f3.data_ptr(), f4.data_ptr())
-        ctx.fhalf = (f3.dtype == torch.float16, f4.dtype == torch.float16)      # ops.fm_rows_half: maps consumed as stored
-        return a
-
-    @staticmethod
-    def backward(ctx, da):
-        X3, X4, h0, h1, w3, w4, w1, w2, pix = ctx.saved_tensors
-        s2, s3, s4 = ctx.shapes
-        dev = da.device
-        n = int(pix.shape[0])
-        k3, c4 = int(X3.shape[1]), int(s4[1])
-        da = da.contiguous()
-        dw2 = _wgrad(da, h1, w2)
-        dh1 = _gemm_t(da, w2)
-        dw1 = _wgrad(dh1, h0, w1)
-        dh0 = _gemm_t(dh1, w1)
-        dw4 = _wgrad(dh0, X4, w4)
-        dX4 = _gemm_t(dh0, w4)
-        dX3p = dX4[:, :k3].contiguous()
-        df4, fin4 = (_row_grad_buffer_h if ctx.fhalf[1] else _row_grad_buffer)(ctx.fptrs[1], s4, dev)
-        if DET_SCATTER:
-            _det_scatter_rows(dX4[:, k3:], k3 + c4, c4, 1, pix, None, n, df4, c4)
-        else:
-            L.call("arco_scatter_add_rows", L.ptr(dX4[:, k3:]), k3 + c4, c4, None, L.ptr(pix), n, None, 1.0, L.ptr(df4), c4)
-        r = fin4(pix, n)
-        if ctx.fhalf[1]:
-            df4 = r
-        dw3 = _wgrad(dX3p, X3, w3)
-        y, _ = ops.conv_raw(dX3p, k3, k3, ops.pack_weight(w3, 1, 1), k3, 1, 1, n, 1, residual=dX3p, ld_res=k3)
-        dX3 = y.permute(0, 2, 3, 1).reshape(n, k3)
-        c2, c3 = int(s2[1]), int(s3[1])
-        dx2p = torch.zeros((s2[0], *s2[2:], c2), dtype=torch.float32, device=dev)
-        df3, fin3 = (_row_grad_buffer_h if ctx.fhalf[0] else _row_grad_buffer)(ctx.fptrs[0], s3, dev)
-        if DET_SCATTER:
-            idx8 = torch.empty(8 * n, dtype=torch.int64, device=dev)
-            w8 = torch.empty(8 * n, dtype=torch.float32, device=dev)
-            L.call("arco_corner_rows3d", L.ptr(pix), n, s2[2], s2[3], s2[4], s3[2], s3[3], s3[4], L.ptr(idx8), L.ptr(w8))
-            _det_scatter_rows(dX3, k3, c2, 8, idx8, w8, 8 * n, dx2p, c2)
-            _det_scatter_rows(dX3[:, c2:], k3, c3, 1, pix, None, n, df3, c3)
-        else:
-            L.call("arco_scatter_upcat_rows3d", L.ptr(dX3), k3, L.ptr(pix), n, L.ptr(dx2p), c2, c2, s2[2], s2[3], s2[4],
-                   L.ptr(df3), c3, c3, s3[2], s3[3], s3[4])
-        r = fin3(pix, n)
-        if ctx.fhalf[0]:
-            df3 = r
-        return (dx2p.movedim(-1, 1), df3.movedim(-1, 1), df4.movedim(-1, 1), dw3, dw4, dw1, dw2, None)
-
-
-def lazy_head3d(x2p, f3, f4, fea3_weight, fea4_weight, q1_weight, q2_weight, pix):
-    return LazyHead3dFn.apply(x2p, f3, f4, fea3_weight, fea4_weight, q1_weight, q2_weight, pix)
-
-
-class LazyTeacher3D:
-    """Teacher side of the 3-D step: prototype_c = W4 . cat((W3+I) . mean_c(cat(up(x2p), f3)), mean_c(f4)) with the
-    class mask pushed through the trilinear adjoint; key rows evaluated at the key voxels only."""
-
-    def __init__(self, x2p, f3, f4, w3, w4):
-        self.x2p, self.f3, self.f4, self.w3, self.w4 = x2p, f3, f4, w3, w4
+    def __init__(self, lo, maps, fea_weights):
+        self.lo, self.maps, self.feas = lo, list(maps), list(fea_weights)
 
     @torch.no_grad()
     def prototypes(self, pl):
-        lo, ldlo = rows_view(self.x2p)
-        r3, ld3 = rows_view(self.f3)
-        r4, ld4 = rows_view(self.f4)
-        nb, c2, d2, h2, w2_ = (int(v) for v in self.x2p.shape)
-        c3, d3, h3, w3_ = (int(v) for v in self.f3.shape[1:])
-        c4 = int(self.f4.shape[1])
-        C, k3 = pl.C, c2 + c3
+        ts = [self.lo, *self.maps]
+        rv = [rows_view(t) for t in ts]
+        nb, C = int(self.lo.shape[0]), pl.C
         wm, Cp = _class_weights(pl)
-        n_lo = nb * d2 * h2 * w2_
-        wlo = torch.empty((n_lo, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_trilinear_bwd", L.ptr(wm), Cp, nb, d2, h2, w2_, Cp, d3, h3, w3_, L.ptr(wlo), Cp)
-        R = _ceil(C, 16)
-        S3 = torch.zeros((R, k3), dtype=torch.float32, device=pl.dev)
-        _wsum(lo, ldlo, wlo, Cp, n_lo, C, c2, pl.totals, S3, k3)
-        _wsum(r3, ld3, wm, Cp, pl.n_pix, C, c3, pl.totals, S3[:, c2:], k3)
-        y3, _ = ops.conv_raw(S3, k3, k3, ops.pack_weight(self.w3, 1, 0), k3, 1, 1, R, 1, residual=S3, ld_res=k3)
-        S4 = torch.zeros((R, k3 + c4), dtype=torch.float32, device=pl.dev)
-        S4[:, :k3] = y3.permute(0, 2, 3, 1).reshape(R, k3)
-        _wsum(r4, ld4, wm, Cp, pl.n_pix, C, c4, pl.totals, S4[:, k3:], k3 + c4)
-        return _gemm(S4, self.w4)[:C].contiguous()
-
-    @torch.no_grad()
-    def rows(self, pix):
-        return _rows3d_forward(self.x2p, self.f3, self.f4, self.w3, self.w4, pix)[2]
-
-
-# ---------------------------------------------------------------------------------------------------------------------------
-# The 3-D head with the 56x56x40 level lazy too (round 6).  Above that level everything is per-voxel, so a sampled voxel needs
-# exactly its EIGHT trilinear corners of x2p = fea2(cat(up(x1p), f2)) + cat(...): 8 n rows of 224 channels instead of the dense
-# 501 760-row map (450 MB at the LA size: the step's longest GEMM launch writes it, its prototype sums, its resize adjoint, its
-# data and weight gradients read it - for ~1 % of its rows).  x1p = fea1(...)+... [B,192,28,28,20] stays dense.
-# ---------------------------------------------------------------------------------------------------------------------------
-def _rows3d_l3_forward(x1p, f2, f3, f4, w2, w3, w4, pix):
-    """corner rows idx8 (at f2's resolution) of every sampled voxel; X2 = cat(trilinear(x1p), f2) on them; X2p = fea2(X2)+X2;
-    X3 = cat(trilinear blend of X2p's eight rows, f3[pix]); then as _rows3d_forward.  Returns (X2, X3, X4, idx8, w8, fea4(X4))."""
-    dev = pix.device
-    lo, ldlo = rows_view(x1p)
-    r2, ld2 = rows_view(f2)
-    r3, ld3 = rows_view(f3)
-    r4, ld4 = rows_view(f4)
-    nb, c1, d1, h1, w1_ = (int(v) for v in x1p.shape)
-    c2, d2, h2, w2_ = (int(v) for v in f2.shape[1:])
-    c3, d3, h3, w3_ = (int(v) for v in f3.shape[1:])
-    c4 = int(f4.shape[1])
-    n = int(pix.shape[0])
-    k2 = c1 + c2
-    k3 = k2 + c3
-    idx8 = torch.empty(8 * n, dtype=torch.int64, device=dev)
-    w8 = torch.empty(8 * n, dtype=torch.float32, device=dev)
-    L.call("arco_corner_rows3d", L.ptr(pix), n, d2, h2, w2_, d3, h3, w3_, L.ptr(idx8), L.ptr(w8))
-    X2 = torch.empty((8 * n, k2), dtype=torch.float32, device=dev)
-    L.call("arco_gather_upcat_rows3d_h" if r2.dtype == torch.float16 else "arco_gather_upcat_rows3d",
-           L.ptr(lo), ldlo, c1, d1, h1, w1_, L.ptr(r2), ld2, c2, d2, h2, w2_, L.ptr(idx8), 8 * n, L.ptr(X2), k2)
-    X2p = _fea_rows(X2, w2, 0)
-    X3 = torch.empty((n, k3), dtype=torch.float32, device=dev)
-    L.call("arco_lerp8_cat_rows3d_h" if r3.dtype == torch.float16 else "arco_lerp8_cat_rows3d",
-           L.ptr(X2p), k2, k2, d2, h2, w2_, L.ptr(r3), ld3, c3, d3, h3, w3_, L.ptr(pix), n, L.ptr(X3), k3)
-    y3, _ = ops.conv_raw(X3, k3, k3, ops.pack_weight(w3, 1, 0), k3, 1, 1, n, 1, residual=X3, ld_res=k3)
-    X4 = torch.empty((n, k3 + c4), dtype=torch.float32, device=dev)
-    X4[:, :k3] = y3.permute(0, 2, 3, 1).reshape(n, k3)
-    L.call("arco_gather_rows_h" if r4.dtype == torch.float16 else "arco_gather_rows",
-           L.ptr(r4), ld4, c4, None, L.ptr(pix), None, 0, n, L.ptr(X4[:, k3:]), k3 + c4)
-    return X2, X3, X4, idx8, w8, _gemm(X4, w4)
-
-
-class LazyHead3dL3Fn(torch.autograd.Function):
-    """Row-sparse student head of the 3-D step with fea2 evaluated on rows too (model_3D.py:46-58, train_arco_3d.py:289-296): inputs
-    x1p = fea1(.)+. [B,192,28,28,20] (dense), f2 [B,32,56,56,40], f3, f4 [B,16,112,112,80].  The gradient becomes dense again from the
-    28x28x20 level down (48 MB); f2's, f3's and f4's are row scatters (order-independent by default, DET_SCATTER)."""
-
-    @staticmethod
-    def forward(ctx, x1p, f2, f3, f4, w2, w3, w4, w1, wq2, pix):
-        X2, X3, X4, idx8, w8, h0 = _rows3d_l3_forward(x1p, f2, f3, f4, w2, w3, w4, pix)
-        h1 = _gemm(h0, w1)
-        a = _gemm(h1, wq2)
-        ctx.save_for_backward(X2, X3, X4, h0, h1, w2, w3, w4, w1, wq2, pix, idx8, w8)
-        ctx.shapes = (tuple(x1p.shape), tuple(f2.shape), tuple(f3.shape), tuple(f4.shape))
-        ctx.fptrs = (f2.data_ptr(), f3.data_ptr(), f4.data_ptr())
-        ctx.fhalf = (f2.dtype == torch.float16, f3.dtype == torch.float16, f4.dtype == torch.float16)
-        return a
-
-    @staticmethod
-    def backward(ctx, da):
-        X2, X3, X4, h0, h1, w2, w3, w4, w1, wq2, pix, idx8, w8 = ctx.saved_tensors
-        s1, s2, s3, s4 = ctx.shapes
-        dev = da.device
-        n = int(pix.shape[0])
-        k2, k3 = int(X2.shape[1]), int(X3.shape[1])
-        c1, c2, c3, c4 = int(s1[1]), int(s2[1]), int(s3[1]), int(s4[1])
-        da = da.contiguous()
-        dwq2 = _wgrad(da, h1, wq2)
-        dh1 = _gemm_t(da, wq2)
-        dw1 = _wgrad(dh1, h0, w1)
-        dh0 = _gemm_t(dh1, w1)
-        dw4 = _wgrad(dh0, X4, w4)
-        dX4 = _gemm_t(dh0, w4)
-        dX3p = dX4[:, :k3].contiguous()
-
-        def scatter(src, ld_src, C, idx, n_e, ptr, shape, half):
-            buf, fin = (_row_grad_buffer_h if half else _row_grad_buffer)(ptr, shape, dev)
-            if DET_SCATTER:
-                _det_scatter_rows(src, ld_src, C, 1, idx, None, n_e, buf, C)
+        wts = [(wm, pl.n_pix)]              # (class-weight rows, row count) of every tensor, walking from the finest map down
+        for t, fine in zip(ts[-2::-1], ts[:0:-1]):
+            sp, sp_fine = tuple(t.shape[2:]), tuple(fine.shape[2:])
+            if sp == sp_fine:
+                wts.append(wts[-1])
+                continue
+            w = torch.empty((nb * math.prod(sp), Cp), dtype=torch.float32, device=pl.dev)
+            if len(sp) == 2:
+                L.call("arco_bilinear_bwd", L.ptr(wts[-1][0]), Cp, nb, *sp, Cp, *sp_fine, L.ptr(w), Cp, 0)
             else:
-                L.call("arco_scatter_add_rows", L.ptr(src), ld_src, C, None, L.ptr(idx), n_e, None, 1.0, L.ptr(buf), C)
-            r = fin(idx, n_e)
-            return r if half else buf
-        df4 = scatter(dX4[:, k3:], k3 + c4, c4, pix, n, ctx.fptrs[2], s4, ctx.fhalf[2])
-        dw3 = _wgrad(dX3p, X3, w3)
-        y, _ = ops.conv_raw(dX3p, k3, k3, ops.pack_weight(w3, 1, 1), k3, 1, 1, n, 1, residual=dX3p, ld_res=k3)
-        dX3 = y.permute(0, 2, 3, 1).reshape(n, k3)
-        df3 = scatter(dX3[:, k2:], k3, c3, pix, n, ctx.fptrs[1], s3, ctx.fhalf[1])
-        dX2p = torch.empty((8 * n, k2), dtype=torch.float32, device=dev)
-        L.call("arco_lerp8_rows3d_bwd", L.ptr(dX3), k3, k2, L.ptr(w8), n, L.ptr(dX2p), k2)
-        dw2 = _wgrad(dX2p, X2, w2)
-        dX2 = _fea_rows(dX2p, w2, 1)
-        df2 = scatter(dX2[:, c1:], k2, c2, idx8, 8 * n, ctx.fptrs[0], s2, ctx.fhalf[0])
-        dx1p = torch.zeros((s1[0], *s1[2:], c1), dtype=torch.float32, device=dev)
-        if DET_SCATTER:
-            idx64 = torch.empty(64 * n, dtype=torch.int64, device=dev)
-            w64 = torch.empty(64 * n, dtype=torch.float32, device=dev)
-            L.call("arco_corner_rows3d", L.ptr(idx8), 8 * n, s1[2], s1[3], s1[4], s2[2], s2[3], s2[4], L.ptr(idx64), L.ptr(w64))
-            _det_scatter_rows(dX2, k2, c1, 8, idx64, w64, 64 * n, dx1p, c1)
-        else:       # (the fp32-atomic adjoint of the gather: lo part only - dhi = a scratch row sink of the right shape)
-            sink = torch.zeros((s2[0], *s2[2:], c2), dtype=torch.float32, device=dev)
-            L.call("arco_scatter_upcat_rows3d", L.ptr(dX2), k2, L.ptr(idx8), 8 * n, L.ptr(dx1p), c1, c1, s1[2], s1[3], s1[4],
-                   L.ptr(sink), c2, c2, s2[2], s2[3], s2[4])
-        return (dx1p.movedim(-1, 1), df2.movedim(-1, 1), df3.movedim(-1, 1), df4.movedim(-1, 1), dw2, dw3, dw4, dw1, dwq2, None)
-
-
-def lazy_head3d_l3(x1p, f2, f3, f4, fea2_weight, fea3_weight, fea4_weight, q1_weight, q2_weight, pix):
-    return LazyHead3dL3Fn.apply(x1p, f2, f3, f4, fea2_weight, fea3_weight, fea4_weight, q1_weight, q2_weight, pix)
-
-
-class LazyTeacher3DL3:
-    """Teacher side with the 56x56x40 level lazy too: prototype_c = W4 . cat((W3+I) . cat((W2+I) . cat(S(x1p; w''), S(f2; w')), S(f3; w)),
-    S(f4; w)) with S(t; w) = the class-weighted row sums of t and the class mask w pushed through the trilinear adjoint once (w', the
-    56x56x40 level) and twice (w'', the 28x28x20 level); key rows evaluated at the key voxels only."""
-
-    def __init__(self, x1p, f2, f3, f4, w2, w3, w4):
-        self.x1p, self.f2, self.f3, self.f4, self.w2, self.w3, self.w4 = x1p, f2, f3, f4, w2, w3, w4
-
-    @torch.no_grad()
-    def prototypes(self, pl):
-        r1, ld1 = rows_view(self.x1p)
-        r2, ld2 = rows_view(self.f2)
-        r3, ld3 = rows_view(self.f3)
-        r4, ld4 = rows_view(self.f4)
-        nb, c1, d1, h1, w1_ = (int(v) for v in self.x1p.shape)
-        c2, d2, h2, w2_ = (int(v) for v in self.f2.shape[1:])
-        c3, d3, h3, w3_ = (int(v) for v in self.f3.shape[1:])
-        c4 = int(self.f4.shape[1])
-        C, k2 = pl.C, c1 + c2
-        k3 = k2 + c3
-        wm, Cp = _class_weights(pl)
-        n2, n1 = nb * d2 * h2 * w2_, nb * d1 * h1 * w1_
-        wl2 = torch.empty((n2, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_trilinear_bwd", L.ptr(wm), Cp, nb, d2, h2, w2_, Cp, d3, h3, w3_, L.ptr(wl2), Cp)
-        wl1 = torch.empty((n1, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_trilinear_bwd", L.ptr(wl2), Cp, nb, d1, h1, w1_, Cp, d2, h2, w2_, L.ptr(wl1), Cp)
+                L.call("arco_trilinear_bwd", L.ptr(wts[-1][0]), Cp, nb, *sp, Cp, *sp_fine, L.ptr(w), Cp)
+            wts.append((w, int(w.shape[0])))
+        wts.reverse()
         R = _ceil(C, 16)
-        S2 = torch.zeros((R, k2), dtype=torch.float32, device=pl.dev)
-        _wsum(r1, ld1, wl1, Cp, n1, C, c1, pl.totals, S2, k2)
-        _wsum(r2, ld2, wl2, Cp, n2, C, c2, pl.totals, S2[:, c1:], k2)
-        S3 = torch.zeros((R, k3), dtype=torch.float32, device=pl.dev)
-        S3[:, :k2] = _fea_rows(S2, self.w2, 0)
-        _wsum(r3, ld3, wm, Cp, pl.n_pix, C, c3, pl.totals, S3[:, k2:], k3)
-        y3, _ = ops.conv_raw(S3, k3, k3, ops.pack_weight(self.w3, 1, 0), k3, 1, 1, R, 1, residual=S3, ld_res=k3)
-        S4 = torch.zeros((R, k3 + c4), dtype=torch.float32, device=pl.dev)
-        S4[:, :k3] = y3.permute(0, 2, 3, 1).reshape(R, k3)
-        _wsum(r4, ld4, wm, Cp, pl.n_pix, C, c4, pl.totals, S4[:, k3:], k3 + c4)
-        return _gemm(S4, self.w4)[:C].contiguous()
+        cs = [int(t.shape[1]) for t in ts]
+
+        def wsum(i, out, ldo):
+            (r, ld), (w, n_t) = rv[i], wts[i]
+            _wsum(r, ld, w, Cp, n_t, C, cs[i], pl.totals, out, ldo)
+        k = cs[0] + cs[1]
+        S = torch.zeros((R, k), dtype=torch.float32, device=pl.dev)            # lo and the coarsest map share the first block
+        wsum(0, S, k)
+        wsum(1, S[:, cs[0]:], k)
+        for i in range(2, len(ts)):                                            # every finer map joins fea_i(S)+S
+            Sn = torch.zeros((R, k + cs[i]), dtype=torch.float32, device=pl.dev)
+            Sn[:, :k] = _fea_rows(S, self.feas[i - 2], 0)
+            wsum(i, Sn[:, k:], k + cs[i])
+            S, k = Sn, k + cs[i]
+        return _gemm(S, self.feas[-1])[:C].contiguous()
 
     @torch.no_grad()
     def rows(self, pix):
-        return _rows3d_l3_forward(self.x1p, self.f2, self.f3, self.f4, self.w2, self.w3, self.w4, pix)[5]
-
-
-class LazyTeacher2DL2:
-    """Two-level lazy teacher (default of the 2-D step): also fea3 is never evaluated densely.
-    prototype_c = W4 . cat((W3+I) . mean_c(cat(up(x2p), f3)), mean_c(f4)), the class mask being pushed through
-    TWO bilinear adjoints (256^2 -> 128^2 -> 64^2); key rows through the two-level row path."""
-
-    def __init__(self, x2p, f3, f4, w3, w4):
-        self.x2p, self.f3, self.f4, self.w3, self.w4 = x2p, f3, f4, w3, w4
-
-    @torch.no_grad()
-    def prototypes(self, pl):
-        lo, ldlo = rows_view(self.x2p)
-        r3, ld3 = rows_view(self.f3)
-        r4, ld4 = rows_view(self.f4)
-        nb, c2, h2, w2_ = (int(v) for v in self.x2p.shape)
-        c3, h3, w3_ = (int(v) for v in self.f3.shape[1:])
-        c4, h4, w4_ = (int(v) for v in self.f4.shape[1:])
-        C, k3 = pl.C, c2 + c3
-        wm, Cp = _class_weights(pl)
-        w3l = torch.empty((nb * h3 * w3_, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_bilinear_bwd", L.ptr(wm), Cp, nb, h3, w3_, Cp, h4, w4_, L.ptr(w3l), Cp, 0)
-        w2l = torch.empty((nb * h2 * w2_, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_bilinear_bwd", L.ptr(w3l), Cp, nb, h2, w2_, Cp, h3, w3_, L.ptr(w2l), Cp, 0)
-        R = _ceil(C, 16)
-        S3 = torch.zeros((R, k3), dtype=torch.float32, device=pl.dev)
-        _wsum(lo, ldlo, w2l, Cp, nb * h2 * w2_, C, c2, pl.totals, S3, k3)
-        _wsum(r3, ld3, w3l, Cp, nb * h3 * w3_, C, c3, pl.totals, S3[:, c2:], k3)
-        y3, _ = ops.conv_raw(S3, k3, k3, ops.pack_weight(self.w3, 1, 0), k3, 1, 1, R, 1, residual=S3, ld_res=k3)
-        S4 = torch.zeros((R, k3 + c4), dtype=torch.float32, device=pl.dev)
-        S4[:, :k3] = y3.permute(0, 2, 3, 1).reshape(R, k3)
-        _wsum(r4, ld4, wm, Cp, pl.n_pix, C, c4, pl.totals, S4[:, k3:], k3 + c4)
-        return _gemm(S4, self.w4)[:C].contiguous()
-
-    @torch.no_grad()
-    def rows(self, pix):
-        return _rows2d_forward(self.x2p, self.f3, self.f4, self.w3, self.w4, pix)[4]
-
-
-class LazyTeacher2DL3:
-    """Three-level lazy teacher (with --head_levels 3): fea2 is never evaluated densely either.  prototype_c =
-    W4 . cat((W3+I) . cat((W2+I) . mean_c(cat(up(x1p), f2)), mean_c(f3)), mean_c(f4)): every map is linear in the feature
-    maps, so the class mask is pushed through THREE bilinear adjoints (256^2 -> 128^2 -> 64^2 -> 32^2) and the weighted row
-    sums run on x1p, f2, f3, f4 (66 MB of reads instead of the dense 117 MB fea2 output, which is not built at all); key
-    rows through the three-level row path."""
-
-    def __init__(self, x1p, f2, f3, f4, w2, w3, w4):
-        self.x1p, self.f2, self.f3, self.f4, self.w2, self.w3, self.w4 = x1p, f2, f3, f4, w2, w3, w4
-
-    @torch.no_grad()
-    def prototypes(self, pl):
-        lo, ldlo = rows_view(self.x1p)
-        r2, ld2 = rows_view(self.f2)
-        r3, ld3 = rows_view(self.f3)
-        r4, ld4 = rows_view(self.f4)
-        nb, c1, h1, w1_ = (int(v) for v in self.x1p.shape)
-        c2, h2, w2_ = (int(v) for v in self.f2.shape[1:])
-        c3, h3, w3_ = (int(v) for v in self.f3.shape[1:])
-        c4, h4, w4_ = (int(v) for v in self.f4.shape[1:])
-        C, k2 = pl.C, c1 + c2
-        k3 = k2 + c3
-        wm, Cp = _class_weights(pl)
-        w3l = torch.empty((nb * h3 * w3_, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_bilinear_bwd", L.ptr(wm), Cp, nb, h3, w3_, Cp, h4, w4_, L.ptr(w3l), Cp, 0)
-        w2l = torch.empty((nb * h2 * w2_, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_bilinear_bwd", L.ptr(w3l), Cp, nb, h2, w2_, Cp, h3, w3_, L.ptr(w2l), Cp, 0)
-        w1l = torch.empty((nb * h1 * w1_, Cp), dtype=torch.float32, device=pl.dev)
-        L.call("arco_bilinear_bwd", L.ptr(w2l), Cp, nb, h1, w1_, Cp, h2, w2_, L.ptr(w1l), Cp, 0)
-        R = _ceil(C, 16)
-        S2 = torch.zeros((R, k2), dtype=torch.float32, device=pl.dev)
-        _wsum(lo, ldlo, w1l, Cp, nb * h1 * w1_, C, c1, pl.totals, S2, k2)
-        _wsum(r2, ld2, w2l, Cp, nb * h2 * w2_, C, c2, pl.totals, S2[:, c1:], k2)
-        S3 = torch.zeros((R, k3), dtype=torch.float32, device=pl.dev)
-        S3[:, :k2] = _fea_rows(S2, self.w2, 0)
-        _wsum(r3, ld3, w3l, Cp, nb * h3 * w3_, C, c3, pl.totals, S3[:, k2:], k3)
-        S4 = torch.zeros((R, k3 + c4), dtype=torch.float32, device=pl.dev)
-        S4[:, :k3] = _fea_rows(S3, self.w3, 0)
-        _wsum(r4, ld4, wm, Cp, pl.n_pix, C, c4, pl.totals, S4[:, k3:], k3 + c4)
-        return _gemm(S4, self.w4)[:C].contiguous()
-
-    @torch.no_grad()
-    def rows(self, pix):
-        return _rows3lvl_forward(self.x1p, self.f2, self.f3, self.f4, self.w2, self.w3, self.w4, pix)[7]
+        rows = _rows2d if self.lo.dim() == 4 else _rows3d
+        return _gemm(rows(self.lo, self.maps, self.feas, pix)[0][-1], self.feas[-1])

@@ -47,7 +47,7 @@ class FeatureExtractor(nn.Module):
 
     def forward_lowres1(self, fea_list):
         """Up to fea1 (second level): returns (fea1(x)+x, f2, f3, f4) for the three-level row-sparse head
-        (arco_amd.head.lazy_head3); the same commuted evaluation as forward_lowres2's first level."""
+        (arco_amd.head.lazy_head2d with three maps); the same commuted evaluation as forward_lowres2's first level."""
         f = [ops.to_channels_last(t) for t in fea_list]
         x = ops.conv(f[0], self.fea0.weight, None, residual=True)
         c = int(x.shape[1])

@@ -43,7 +43,7 @@ class FeatureExtractor_3d(nn.Module):
         return x, f[3], f[4]
 
     def forward_lowres1(self, fea_list):
-        """Up to fea1 (the 28x28x20 level): (fea1(x)+x, f2, f3, f4) for the three-level row-sparse head (arco_amd.head.LazyHead3dL3Fn):
+        """Up to fea1 (the 28x28x20 level): (fea1(x)+x, f2, f3, f4) for the three-level row-sparse head (arco_amd.head.lazy_head3d with three maps):
         fea2's 224-channel map at 56x56x40 - 450 MB at the LA size, of which a step reads ~1 % of the rows - is not evaluated densely."""
         f = [ops.to_channels_last(t) for t in fea_list]
         x = ops.conv(f[0], self.fea0.weight, None, residual=True)

@@ -1755,12 +1755,12 @@ class logits_only:
 
 class fm_rows_half(logits_only):
     """`with ops.fm_rows_half():` - a V-Net forward inside (f16 mode) casts its three LOW-resolution feature maps to fp32 and hands
-    the two full-resolution ones out as stored (f16): the row-sparse heads (arco_amd.head.lazy_head3d, LazyTeacher3D) read rows /
+    the two full-resolution ones out as stored (f16): the row-sparse heads (arco_amd.head.lazy_head3d, LazyTeacher) read rows /
     weighted row sums of those two straight from the f16 maps and return a row-sparse f16 gradient - no dense cast of a
     full-resolution map in either direction (they were 0.64 ms of the LiTS-shaped step).
 
     `with ops.fm_rows_half(k):` - a U-Net forward inside (f16 mode) hands its k finest feature maps out as stored and casts the
-    others (and the bottleneck) to fp32: the 2-D row-sparse heads (arco_amd.head.lazy_head / lazy_head2 / lazy_head3 and the
+    others (and the bottleneck) to fp32: the 2-D row-sparse heads (arco_amd.head.lazy_head2d and the
     lazy teachers) read rows of exactly the maps their depth never touches densely (train_arco_2d --fm_rows f16).  The count
     travels in FM_CAST as ('keep', k) - a tuple, since 1 == True would alias the default in the graphs' capture keys; the V-Net
     reads any value other than 'lowres' / False as "cast all"."""

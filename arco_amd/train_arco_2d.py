@@ -325,12 +325,14 @@ class ArcoStep2D(LossScaleGuard):
         a, kfe = self.args, self.k_feature_extractor
         if getattr(a, "dense_teacher", 0) or dense:
             return kfe(fm_t), None
-        if getattr(a, "head_levels", 3) == 1:
-            x3p_t, f4_t = kfe.forward_lowres(fm_t)
-            return None, head.LazyTeacher2D(x3p_t, f4_t, kfe.fea4.weight)
-        if getattr(a, "teacher_levels", 2) == 3:
-            return None, head.LazyTeacher2DL3(*kfe.forward_lowres1(fm_t), kfe.fea2.weight, kfe.fea3.weight, kfe.fea4.weight)
-        return None, head.LazyTeacher2DL2(*kfe.forward_lowres2(fm_t), kfe.fea3.weight, kfe.fea4.weight)
+        levels = 1 if getattr(a, "head_levels", 3) == 1 else 3 if getattr(a, "teacher_levels", 2) == 3 else 2
+        return None, head.LazyTeacher(*self._lowres(kfe, fm_t, levels))
+
+    @staticmethod
+    def _lowres(fe, fm, levels):
+        """(lo, maps, fea weights) of FeatureExtractor `fe` as the row-sparse head and the lazy teacher of `levels` levels take them."""
+        lo, *maps = (fe.forward_lowres, fe.forward_lowres2, fe.forward_lowres1)[levels - 1](fm)
+        return lo, maps, [f.weight for f in (fe.fea2, fe.fea3, fe.fea4)[3 - levels:]]
 
     def step(self, l_data, l_label, u_data, epoch_num=0, max_epoch=1):
         """One iteration.  The mixing strategy of --apply_aug (augment.generate_unsup_data) and batch_transform (8-bit PIL
@@ -497,12 +499,9 @@ class ArcoStep2D(LossScaleGuard):
         fm_all = adist.mark_heads_done(fm_all, self.optimizer, self.heads_start)
         if dense:
             rep_all = self.q_rep(self.q_feature_extractor(fm_all))       # :324-325,330
-        elif getattr(a, "head_levels", 3) == 1:
-            x3p, f4 = self.q_feature_extractor.forward_lowres(fm_all)
-        elif getattr(a, "head_levels", 3) == 3:
-            x1p, f2, f3, f4 = self.q_feature_extractor.forward_lowres1(fm_all)
         else:
-            x2p, f3, f4 = self.q_feature_extractor.forward_lowres2(fm_all)
+            hl = getattr(a, "head_levels", 3)
+            s_low = self._lowres(self.q_feature_extractor, fm_all, hl if hl in (1, 3) else 2)
         # supervised CE + Dice and confidence-weighted unsupervised CE (:336-340): they need neither the
         # counters nor the samples - queued before the host blocks.  The equivariance term follows the sampler draw below.
         # k4*loss_q (revisiting loss; no gradient path to any parameter) only with --revisit 1.
@@ -605,18 +604,8 @@ class ArcoStep2D(LossScaleGuard):
         else:
             if dense:
                 A_all = C_.GatherRowsFn.apply(rep_all, plan.anchor_pix)
-            elif getattr(a, "head_levels", 3) == 1:
-                A_all = head.lazy_head(x3p, f4, self.q_feature_extractor.fea4.weight,
-                                       self.q_representation[0].weight, self.q_representation[1].weight,
-                                       plan.anchor_pix)
-            elif getattr(a, "head_levels", 3) == 3:
-                qfe = self.q_feature_extractor
-                A_all = head.lazy_head3(x1p, f2, f3, f4, qfe.fea2.weight, qfe.fea3.weight, qfe.fea4.weight,
-                                        self.q_representation[0].weight, self.q_representation[1].weight, plan.anchor_pix)
             else:
-                A_all = head.lazy_head2(x2p, f3, f4, self.q_feature_extractor.fea3.weight,
-                                        self.q_feature_extractor.fea4.weight, self.q_representation[0].weight,
-                                        self.q_representation[1].weight, plan.anchor_pix)
+                A_all = head.lazy_head2d(*s_low, self.q_representation[0].weight, self.q_representation[1].weight, plan.anchor_pix)
             reco_loss, _ = C_.contrast_infonce(plan, A_all, self.memobank, temp=0.5)   # :394-398 (temp default)
             if self.keep_debug:
                 self.debug = dict(plan=plan, A_all=A_all.detach(), banks=[m[0] for m in self.memobank])

@@ -34,7 +34,7 @@ from .train_arco_2d import build_parser as _build_parser_2d
 PASS_SIDE = min(3, int(os.environ.get("ARCO_TEACHER_SIDE", "4")))
 LISTS_SIDE = int(os.environ.get("ARCO_LISTS_SIDE", "1"))
 # lazy levels of the row-sparse heads: 2 = fea3 / fea4 on rows over the dense 56x56x40 map of fea2 (rounds 2-5), 3 = fea2 on rows too - the
-# 224-channel map at 56x56x40 (450 MB at the LA size) is never written (head.LazyHead3dL3Fn, round 6)
+# 224-channel map at 56x56x40 (450 MB at the LA size) is never written (head.LazyHead3dFn with three maps, round 6)
 HEAD_LEVELS = int(os.environ.get("ARCO_HEAD3D_LEVELS", "3"))
 # ARCO_U0_SIDE=1: the teacher's first pass beside the grouped student pass (cutout / cutmix; see ArcoStep3D.step).  Opt-in: measured level
 # (LA 21.2-21.3 -> 21.3-21.4 ms, LiTS-f16 13.7 -> 13.6-13.7) - the teacher's two passes stay serial on the second stream, which is then the
@@ -69,6 +69,12 @@ def build_parser():
                         'its loss only enters the objective at iteration 0 there (:390-393), afterwards it is a logged '
                         'value and a BatchNorm running-statistics update')
     return p
+
+
+def _lowres(fe, fm):
+    """(lo, maps, fea weights) of FeatureExtractor_3d `fe` as the row-sparse head and the lazy teacher of HEAD_LEVELS levels take them."""
+    lo, *maps = (fe.forward_lowres1 if HEAD_LEVELS == 3 else fe.forward_lowres2)(fm)
+    return lo, maps, [f.weight for f in (fe.fea2, fe.fea3, fe.fea4)[HEAD_LEVELS != 3:]]
 
 
 class ArcoStep3D(LossScaleGuard):
@@ -159,9 +165,7 @@ class ArcoStep3D(LossScaleGuard):
 
     @staticmethod
     def _lazy_teacher(kfe, fm_t):
-        if HEAD_LEVELS == 3:
-            return head.LazyTeacher3DL3(*kfe.forward_lowres1(fm_t), kfe.fea2.weight, kfe.fea3.weight, kfe.fea4.weight)
-        return head.LazyTeacher3D(*kfe.forward_lowres2(fm_t), kfe.fea3.weight, kfe.fea4.weight)
+        return head.LazyTeacher(*_lowres(kfe, fm_t))
 
     def q_rep(self, x):
         x = ops.conv(x, self.q_representation[0].weight)
@@ -297,7 +301,7 @@ class ArcoStep3D(LossScaleGuard):
         if dense:
             rep_all = self.q_rep(qfe(fm_s))                              # :289-296,301
         else:
-            s_maps = qfe.forward_lowres1(fm_s) if HEAD_LEVELS == 3 else qfe.forward_lowres2(fm_s)
+            s_low = _lowres(qfe, fm_s)
         if lists_done is not None:
             torch.cuda.current_stream().wait_event(lists_done)
         else:
@@ -370,12 +374,7 @@ class ArcoStep3D(LossScaleGuard):
             A_all = C_.GatherRowsFn.apply(rep_all, plan.anchor_pix)
             reco_loss, _ = C_.contrast_infonce(plan, A_all, self.memobank, temp=0.5)
         else:
-            if HEAD_LEVELS == 3:
-                A_all = head.lazy_head3d_l3(*s_maps, qfe.fea2.weight, qfe.fea3.weight, qfe.fea4.weight, self.q_representation[0].weight,
-                                            self.q_representation[1].weight, plan.anchor_pix)
-            else:
-                A_all = head.lazy_head3d(*s_maps, qfe.fea3.weight, qfe.fea4.weight, self.q_representation[0].weight,
-                                         self.q_representation[1].weight, plan.anchor_pix)
+            A_all = head.lazy_head3d(*s_low, self.q_representation[0].weight, self.q_representation[1].weight, plan.anchor_pix)
             reco_loss, _ = C_.contrast_infonce(plan, A_all, self.memobank, temp=0.5)
         if self.keep_debug and plan.valid_seg > 1 and plan.entries:
             self.debug = dict(plan=plan, A_all=A_all.detach(), banks=[m[0] for m in self.memobank])

@@ -140,13 +140,12 @@ def _head_inputs(levels, seed=3):
 
 
 def _run_head(levels, lo, maps, ws, w1, wq, pix, da):
-    """rows and every gradient of head.lazy_head{,2,3} on the given maps (f16 or fp32)."""
+    """rows and every gradient of head.lazy_head2d on the given maps (f16 or fp32)."""
     from arco_amd import head
     lo_l = lo.clone().requires_grad_(True)
     maps_l = [m.clone().requires_grad_(True) for m in maps]
     par = [w.clone().requires_grad_(True) for w in ws + [w1, wq]]
-    fn = {1: head.lazy_head, 2: head.lazy_head2, 3: head.lazy_head3}[levels]
-    a = fn(lo_l, *maps_l, *par, pix)
+    a = head.lazy_head2d(lo_l, maps_l, par[:levels], par[-2], par[-1], pix)
     a.backward(da)
     return a.detach(), lo_l.grad, [m.grad for m in maps_l], [p.grad for p in par]
 
@@ -160,7 +159,7 @@ def _f16_ulp(y):
 @pytest.mark.parametrize("levels,det,scale", [(1, 2, 16384.0), (2, 2, 16384.0), (3, 2, 16384.0), (3, 2, 256.0),
                                               (1, 0, 16384.0), (2, 0, 16384.0), (3, 0, 16384.0)])
 def test_heads_on_f16_maps_equal_the_heads_on_their_fp32_copies(levels, det, scale, monkeypatch):
-    """lazy_head / lazy_head2 / lazy_head3: an arm with the maps passed as f16 against an arm with the same maps upcast to fp32.
+    """lazy_head2d at 1, 2 and 3 levels: an arm with the maps passed as f16 against an arm with the same maps upcast to fp32.
     (a) anchor rows bit-equal.  (b) order-independent scatter (DET_SCATTER = 2): weight gradients and the dense low-resolution input's
     gradient bit-equal, every f16 map gradient bit-equal to (fp32 gradient * LOSS_SCALE).to(f16) of the fp32 arm - what the dense
     boundary cast computes.  (c) fp32 atomics (DET_SCATTER = 0): fp32 gradients to 1e-5 of the tensor's maximum (the reproducibility
@@ -205,7 +204,7 @@ def test_heads_on_f16_maps_equal_the_heads_on_their_fp32_copies(levels, det, sca
 
 @pytest.mark.parametrize("levels", [1, 2, 3])
 def test_teachers_on_f16_maps_equal_the_teachers_on_their_fp32_copies(levels):
-    """LazyTeacher2D / 2DL2 / 2DL3: rows() and prototypes() bit-equal between f16 maps and their fp32 copies.  prototypes(): the f16
+    """LazyTeacher at 1, 2 and 3 levels: rows() and prototypes() bit-equal between f16 maps and their fp32 copies.  prototypes(): the f16
     form of arco_weighted_row_sum is the same template as the fp32 one (loss_front.hip weighted_row_sum_kernel<NDI, TS>): only the
     load differs (ld4f widens four f16 exactly), the accumulation order, the slab reduction and the finalize are shared - no
     tolerance."""
@@ -216,9 +215,8 @@ def test_teachers_on_f16_maps_equal_the_teachers_on_their_fp32_copies(levels):
     inp = {k: v.to(DEV) for k, v in fx.loss_inputs(9, b=1, n_cls=4, feat=4, spatial=(256, 256)).items()}
     pl = C_.contrast_masks(inp["label_l"], inp["label_u"], inp["prob_l"], inp["prob_u"], inp["low_mask"], inp["high_mask"], 0.97)
     assert pl.n_img == NB
-    cls = {1: head.LazyTeacher2D, 2: head.LazyTeacher2DL2, 3: head.LazyTeacher2DL3}[levels]
-    t16 = cls(lo, *maps, *ws)
-    t32 = cls(lo, *[m.float() for m in maps], *ws)
+    t16 = head.LazyTeacher(lo, maps, ws)
+    t32 = head.LazyTeacher(lo, [m.float() for m in maps], ws)
     r16, r32 = t16.rows(pix), t32.rows(pix)
     assert r16.shape == (int(pix.numel()), 496) and torch.equal(r16, r32) and float(r32.abs().max()) > 0
     p16, p32 = t16.prototypes(pl), t32.prototypes(pl)

@@ -402,7 +402,7 @@ def test_row_sparse_heads_on_f16_feature_maps_equal_the_cast_path():
             leaves = [t.clone().requires_grad_(True) for t in (x2p, w3, w4, w1, w2)]
             f3l, f4l = f3h.clone().requires_grad_(True), f4h.clone().requires_grad_(True)
             f3, f4 = (f3l, f4l) if mode == "half" else (ops.from_half(f3l), ops.from_half(f4l))
-            a = head.lazy_head3d(leaves[0], f3, f4, leaves[1], leaves[2], leaves[3], leaves[4], pix)
+            a = head.lazy_head3d(leaves[0], [f3, f4], leaves[1:3], leaves[3], leaves[4], pix)
             a.backward(da)
             res[mode] = [a.detach()] + [t.grad for t in leaves] + [f3l.grad, f4l.grad]
             assert f3l.grad.dtype == torch.float16 and f4l.grad.dtype == torch.float16
@@ -419,8 +419,8 @@ def test_row_sparse_heads_on_f16_feature_maps_equal_the_cast_path():
         # teacher: prototypes and key rows
         inp = {k: v.to(dev) for k, v in fx.loss_inputs(9, b=1, n_cls=3, feat=16, spatial=sp).items()}
         pl = C_.contrast_masks(inp["label_l"], inp["label_u"], inp["prob_l"], inp["prob_u"], inp["low_mask"], inp["high_mask"], 0.97)
-        t_h = head.LazyTeacher3D(x2p, f3h, f4h, w3, w4)
-        t_c = head.LazyTeacher3D(x2p, ops.from_half(f3h), ops.from_half(f4h), w3, w4)
+        t_h = head.LazyTeacher(x2p, [f3h, f4h], [w3, w4])
+        t_c = head.LazyTeacher(x2p, [ops.from_half(f3h), ops.from_half(f4h)], [w3, w4])
         assert torch.equal(t_h.prototypes(pl), t_c.prototypes(pl))
         assert torch.equal(t_h.rows(pix), t_c.rows(pix))
     finally:

@@ -16,7 +16,7 @@ def wrap(mod, name):
 for n in ("contrast_masks", "contrast_sample", "contrast_enqueue", "contrast_infonce"):
     wrap(C_, n)
 import arco_amd.head as H
-wrap(H, "lazy_head")
+wrap(H, "lazy_head2d")
 _es = torch.cuda.Event.synchronize
 def es(self):
     t0 = time.perf_counter(); r = _es(self); marks.setdefault("event_sync", []).append((time.perf_counter() - t0) * 1e3); return r
