@@ -33,8 +33,10 @@ CONV_MMA = int(__import__('os').environ.get('ARCO_CONV_MMA', '3'))          # MF
                       # 1 / 2 ("f16" / "bf16"): the 3x3x3 convolutions round their operands to f16 / bf16 (BASELINE configs[4])
 HEAD_MMA = 0         # 1 / 2: every 1x1 / 1x1x1 GEMM on fp32 tensors (FeatureExtractor_3d, q_representation, the row-sparse heads: model_3D.py:37-63,
                      # train_arco_3d.py:206-209) rounds its operands to f16 / bf16 in registers (v_mfma_f32_16x16x16_f16, fp32 accumulate; gradient
-                     # operands bf16 for range) - the "contrastive" half of BASELINE configs[4]'s "fp16 MFMA conv + contrastive"; set by
-                     # train_arco_3d --act_dtype f16 (--head_mma).  0: the GEMMs follow CONV_MMA
+                     # operands bf16 for range) - the "contrastive" half of BASELINE configs[4]'s "fp16 MFMA conv + contrastive"; the 3-D
+                     # trainer's --head_mma table (auto: 1 with --act_dtype f16), the 2-D trainer 0.  0: the GEMMs follow CONV_MMA.
+                     # Written - like CONV_MMA, ACT_HALF, LOSS_SCALE and WGRAD_SIDE - by every stepper's constructor, in one place:
+                     # stepper.ArcoStepBase._set_modes
 PROFILE_EVERY = 1    # time every n-th conv launch of an instantiation (bench.py: 7, prime vs the per-step launch counts)
 ACT_HALF = False     # f16 ACTIVATION STORAGE of the volume path (--act_dtype f16 of train_arco_3d, BASELINE configs[4]): the V-Net's
                      # first layer writes f16 and every operator below follows its input's dtype (csrc/conv_h.hip, the *_h entry points);
@@ -633,8 +635,8 @@ def conv_wgrad(dzr, ldz, co, xr, ldx, ci, taps, nb, h, w, like, d3=1, pro=None):
 # (30.1 -> 29.2 ms: two queues hide host launch time), nothing under the default graph replay (30.1-30.6 both ways; LiTS f16
 # 20.5 vs 20.7).  Hence: off by default, kept as a knob (ARCO_WGRAD_SIDE=1..3).
 # Round 6: with the pipelined 3x3x3 kernels the LA step gains 0.3-0.5 ms from mode 3 under graph replay (24.9 / 24.8 / 25.7 -> 24.6 / 24.4 / 25.2 ms,
-# same box, alternating; LiTS-f16 level, the 2-D step 11.0-11.2 -> 12.2-12.3): the 3-D trainer's constructor sets 3, the 2-D trainer's 0,
-# unless ARCO_WGRAD_SIDE is given.
+# same box, alternating; LiTS-f16 level, the 2-D step 11.0-11.2 -> 12.2-12.3): the 3-D trainer's constructor sets 3, the 2-D trainer's 0
+# (both through stepper.ArcoStepBase._set_modes, the one writer of the mode switches), unless ARCO_WGRAD_SIDE is given.
 _WGRAD_SIDE_ENV = __import__('os').environ.get('ARCO_WGRAD_SIDE')
 WGRAD_SIDE = int(_WGRAD_SIDE_ENV) if _WGRAD_SIDE_ENV is not None else 0
 _side = {"stream": None, "keep": [], "dirty": False}

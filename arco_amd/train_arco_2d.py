@@ -18,17 +18,15 @@ import argparse
 import logging
 import contextlib
 import os
-import random
-import sys
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import dist as adist
-from .loss_scale import LossScaleGuard
 from . import _contrast as C_
-from . import augment, glue, graphs, head, ops, optim
+from . import augment, glue, graphs, head, ops, stepper
+from .stepper import ArcoStepBase
 from .tps import RandTPS
 from .model_2D import ISD, FeatureExtractor
 
@@ -180,21 +178,16 @@ SIDE_SYNC = int(os.environ.get("ARCO_SIDE_SYNC", "0"))
 IMG_EARLY = int(os.environ.get("ARCO_IMG_EARLY", "1"))     # see ArcoStep2D.step (with TEACHER_SIDE >= 4)
 
 
-class ArcoStep2D(LossScaleGuard):
+class ArcoStep2D(ArcoStepBase):
     """State + one training step of the 2-D hot path (train_arco_2d.py:147-154,220-253,284-435)."""
 
     def __init__(self, args, device="cuda"):
         self.args = args
         self.dev = torch.device(device)
-        C = args.num_classes
         mma = getattr(args, "conv_mma", "f32x3")
         if mma not in ("f32", "f32x3"):      # no silent fp32 run under a reduced-precision label (the modes exist in 3-D only)
             raise ValueError(f"--conv_mma {mma}: the 2-D step computes in f32x3 or f32; f16 / bf16 operands are a 3-D trainer mode")
-        ops.CONV_MMA = {"f32": 0, "f32x3": 3}[mma]
-        ops.HEAD_MMA = 0                 # (a 3-D trainer of this process may have set the heads' reduced-precision mode)
-        # f16 activation storage of the U-Net: set BOTH ways (a default stepper built after an f16 one in the same process is fp32
-        # again), before the PackPlans - they carry the f16 packs
-        half = getattr(args, "act_dtype", "f32") == "f16"
+        half = getattr(args, "act_dtype", "f32") == "f16"           # f16 activation storage of the U-Net
         rows16 = getattr(args, "fm_rows", "f32") == "f16"
         if rows16 and not half:
             raise ValueError("--fm_rows f16 needs --act_dtype f16: with fp32 activation storage there is no f16 feature map to read rows of")
@@ -206,10 +199,9 @@ class ArcoStep2D(LossScaleGuard):
         if half and (getattr(args, "dense_head", 0) or getattr(args, "revisit", 0)):
             raise ValueError("--act_dtype f16 is not combined with --dense_head 1 / --revisit 1: the dense heads and the revisiting "
                              "term have not been run on the f16 U-Net (use --act_dtype f32)")
-        ops.ACT_HALF = half
-        ops.LOSS_SCALE = float(getattr(args, "loss_scale", 16384.0))
-        if ops._WGRAD_SIDE_ENV is None:
-            ops.WGRAD_SIDE = 0           # (... and the side-stream weight gradients: 11.0-11.2 -> 12.2-12.3 ms on this step)
+        # no reduced-precision heads in 2-D; no side-stream weight gradients (11.0-11.2 -> 12.2-12.3 ms on this step)
+        self._set_modes(conv_mma={"f32": 0, "f32x3": 3}[mma], act_half=half, head_mma=0, wgrad_side=0)
+        # The torch CPU generator is consumed in the reference's order: pool, banks (zeros: no draw), models, heads, one warp.
         self.random_pool = None
         if getattr(args, "revisit", 0):
             # random_pool (:156-159) is drawn before the models are created, like the reference (same CPU-generator order)
@@ -222,49 +214,16 @@ class ArcoStep2D(LossScaleGuard):
             # for the same seed (samplers.skip_randn: 0.4 s of state regeneration for K = 36 at 256 x 256)
             from . import samplers
             samplers.skip_randn(args.K * REP_DIM * int(args.patch_size[0]) * int(args.patch_size[1]))
-        # memory banks (train_arco_2d.py:147-154); device resident from the first enqueue on
-        self.memobank, self.queue_ptrlis, self.queue_size = [], [], []
-        for i in range(C):
-            self.memobank.append([torch.zeros(1, REP_DIM)])
-            self.queue_size.append(args.queue_size if args.queue_size > 0 else 30000)
-            self.queue_ptrlis.append(torch.zeros(1, dtype=torch.long))
-        if args.queue_size <= 0:
-            self.queue_size[0] = 50000
-        self.isd = ISD(K=args.K, m=0.99, Ts=0.01, Tt=0.1, num_classes=C,
+        self._build_banks(lambda: torch.zeros(1, REP_DIM))
+        self.isd = ISD(K=args.K, m=0.99, Ts=0.01, Tt=0.1, num_classes=args.num_classes,
                        latent_pooling_size=args.latent_pooling_size, latent_feature_size=args.latent_feature_size,
                        output_pooling_size=args.output_pooling_size, train_encoder=True, train_decoder=True,
                        in_chns=args.in_chns)
         self.isd = self.isd.to(self.dev)
-        self.model, self.ema_model = self.isd.model, self.isd.ema_model
-        self.q_representation = nn.Sequential(nn.Conv2d(REP_DIM, REP_DIM, kernel_size=1, bias=False),
-                                              nn.Conv2d(REP_DIM, REP_DIM, kernel_size=1, bias=False)).to(self.dev)
-        self.k_feature_extractor = FeatureExtractor(fea_dim=FEA_DIM, output_dim=REP_DIM).to(self.dev)
-        self.q_feature_extractor = FeatureExtractor(fea_dim=FEA_DIM, output_dim=REP_DIM).to(self.dev)
-        adist.broadcast_module_states([self.isd, self.q_representation, self.q_feature_extractor,
-                                       self.k_feature_extractor])
-        params = [p for p in self.model.parameters() if p.requires_grad]
-        params_rep = [p for p in self.q_representation.parameters() if p.requires_grad]
-        params_fea = [p for p in self.q_feature_extractor.parameters() if p.requires_grad]
-        self.heads_start = sum(p.numel() for p in params)     # flat_g[heads_start:] = the heads' gradient bucket (dist.mark_heads_done)
-        self.optimizer = optim.SGDNesterov(params + params_rep + params_fea, lr=args.base_lr, weight_decay=0.0001,
-                                           momentum=0.9, nesterov=True)
-        with torch.no_grad():                                            # :250-253
-            for t, s in zip(self.k_feature_extractor.parameters(), self.q_feature_extractor.parameters()):
-                t.data.copy_(s.data)
-                t.requires_grad = False
-        self.k_fe_ema = optim.EmaPair(self.q_feature_extractor, self.k_feature_extractor)
-        for m in (self.model, self.ema_model, self.q_representation, self.k_feature_extractor,
-                  self.q_feature_extractor):
-            m.train()                                                   # :263-267
-        # packed conv weights: one launch per weight owner per step (ops.PackPlan), refreshed by the owner
-        plan_s = ops.PackPlan([self.model, self.q_representation, self.q_feature_extractor], True, half=[ops.ACT_HALF, False, False])
-        self.optimizer.plans = [plan_s]
-        pairs = self.isd._ensure_ema_pairs()
-        pairs[0].plans = [ops.PackPlan([self.ema_model], False, half=[ops.ACT_HALF])]
-        for pr in pairs[1:]:
-            pr.plans = [ops.PackPlan([], False)]
-        self.k_fe_ema.plans = [ops.PackPlan([self.k_feature_extractor], False)]
-        self.plans = [plan_s] + [pl for pr in pairs for pl in pr.plans] + self.k_fe_ema.plans
+        self._build_heads(nn.Conv2d, FeatureExtractor, FEA_DIM, REP_DIM)
+        # RandTPS of the equivariance term: built here like the reference (:255-261; the constructor draws one warp
+        # from the generators), rebuilt in step() only if the batch size differs
+        self.tps = self._make_tps(2 * args.batch_size, device) if getattr(args, "k2", 0) != 0 else None
         # --fm_rows f16: how many of its finest maps a pass hands out as stored (ops.fm_rows_half(k)) - exactly those its consumer
         # reads as rows only (FeatureExtractor.forward_lowres / _lowres2 / _lowres1 run fp32 GEMMs on the others); the passes that
         # read nothing but the logits cast no map (ops.logits_only).  --fm_rows f32: every pass casts all five, as before.
@@ -274,38 +233,25 @@ class ArcoStep2D(LossScaleGuard):
         self._fm_s = (lambda: ops.fm_rows_half(self.fm_keep_s)) if rows16 else contextlib.nullcontext
         self._fm_t = (lambda: ops.fm_rows_half(self.fm_keep_t)) if rows16 else contextlib.nullcontext
         self._fm_none = ops.logits_only if rows16 else contextlib.nullcontext
-        self.iter_num = 0
         # HIP-event timing of the three contrastive-loss segments: only when a profiler asks for it (bench.py sets
         # profile_loss); a training run records no events (no stream bubbles, nothing accumulates)
         self.profile_loss = False
-        self._t_stream = None
-        self._stats_on_side = False
-        self.keep_debug = False          # tests: keep the last step's plan and anchor rows (self.debug)
         self.loss_events = []
-        # no-grad forwards replayed as HIP graphs (one graph per call site: outputs are static buffers)
-        use_graphs = bool(getattr(args, "graphs", 1))
-        g_train = use_graphs and bool(getattr(args, "graph_train", 0))
-        self.s_train_u = graphs.GraphedTrain(self.model, enabled=g_train)    # student passes: fwd + bwd graphs
-        self.s_train_l = graphs.GraphedTrain(self.model, enabled=g_train)
-        # RandTPS of the equivariance term: built here like the reference (:255-261; the constructor draws one warp
-        # from the generators), rebuilt in step() only if the batch size differs
-        self.tps = None
-        if getattr(args, "k2", 0) != 0:
-            self.tps = RandTPS(args.patch_size[0], args.patch_size[1], batch_size=2 * args.batch_size,
-                               sigma=args.tps_sigma, border_padding=False, random_mirror=True, random_scale=(0.8, 1.2),
-                               mode='affine', device=device)
-        self.batched_passes = bool(getattr(args, "batched_passes", 1))
-        self.s_train_lu = graphs.GraphedTrain(self.model, enabled=g_train)
+        self._t_stream = self._img_stream = None     # side streams, created on first use (self._stream)
+        self._stats_on_side = self._tps_on_side = False
+        use_graphs, g_train = self._build_graphs()
         # the equivariance term's student pass (:415).  ARCO_TEACHER_SIDE >= 3: replayed on the side stream - its forward beside the
         # heads / InfoNCE, its backward beside the main pass's backward - with a gradient buffer of its own (optim.second_grad_views)
         self._tps_side = TEACHER_SIDE >= 3 and g_train
         self.s_train_tps = graphs.GraphedTrain(self.model, enabled=g_train,
                                                grad_views=self.optimizer.second_grad_views() if self._tps_side else None)
-        self.t_fwd_lu = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
-        self.t_fwd_u0 = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
-        self.t_fwd_l = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
-        self.t_fwd_u = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
         self.s_fwd_stats = graphs.GraphedForward(self.model, enabled=use_graphs)
+
+    def _make_tps(self, batch_size, device):
+        """:255-261 (the constructor of RandTPS draws one warp, like the reference)."""
+        a = self.args
+        return RandTPS(a.patch_size[0], a.patch_size[1], batch_size=batch_size, sigma=a.tps_sigma, border_padding=False,
+                       random_mirror=True, random_scale=(0.8, 1.2), mode='affine', device=device)
 
     def fm_rows_note(self):
         """Which feature maps the heads read as f16 rows (for the log line of the f16 mode)."""
@@ -314,10 +260,6 @@ class ArcoStep2D(LossScaleGuard):
         names = ["f0", "f1", "f2", "f3", "f4"]
         return ("--fm_rows f16: f16 rows of %s (student) and %s (teacher), no map cast in the logits-only passes"
                 % (", ".join(names[5 - self.fm_keep_s:]), ", ".join(names[5 - self.fm_keep_t:])))
-
-    def q_rep(self, x):
-        x = ops.conv(x, self.q_representation[0].weight)
-        return ops.conv(x, self.q_representation[1].weight)
 
     def _teacher_heads(self, fm_t, dense):
         """(dense teacher representation or None, lazy teacher or None): the teacher's FeatureExtractor (:321-322) in the form the
@@ -344,11 +286,7 @@ class ArcoStep2D(LossScaleGuard):
         it, and the torch-CPU-generator index replay runs on the host while they execute."""
         a = self.args
         C = a.num_classes
-        if ops.ACT_HALF:
-            self._loss_scale_update()
-        for pl in self.plans:                                            # stale only if someone else touched weights
-            if not pl.valid:
-                pl.refresh()
+        self._step_head()
         dense = getattr(a, "dense_head", 0)
         # randomGeneratorWithLogits (:292-293) is a same-size zoom(order=0) = the identity; then the mixing strategy
         # (:296-297) on the GPU with the reference's host draws; other --apply_aug values leave the batch unchanged
@@ -366,9 +304,7 @@ class ArcoStep2D(LossScaleGuard):
             # side stream beside the teacher's first pass (two 8-image passes, neither of which fills the chip alone).  Its
             # running-statistics updates are postponed (slot 1) and land between those of the l and the u half of the grouped
             # student pass below: the reference's order l, cj2_l, u.
-            if self._t_stream is None:
-                self._t_stream = torch.cuda.Stream()
-            self._t_stream.wait_stream(torch.cuda.current_stream())
+            self._stream("_t_stream").wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._t_stream), torch.no_grad(), ops.bn_defer(0, 1), self._fm_none():
                 self.s_fwd_stats(cj2_l)
         # IMG_EARLY (cutout / cutmix): the IMAGE side of the mixing strategy and of the two batch_transform calls (:296-304) reads no
@@ -379,10 +315,8 @@ class ArcoStep2D(LossScaleGuard):
         # the same boxes once the pseudo-labels exist.
         img_early = bool(IMG_EARLY and stats_early and a.apply_aug in ("cutout", "cutmix"))
         if img_early:
-            if getattr(self, "_img_stream", None) is None:
-                self._img_stream = torch.cuda.Stream()
             mix_desc = augment.draw_boxes(int(u_data.shape[0]), tuple(int(v) for v in u_data.shape[2:]))
-            self._img_stream.wait_stream(torch.cuda.current_stream())
+            self._stream("_img_stream").wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._img_stream):
                 u_mix = augment.mix_images(u_data, a.apply_aug, mix_desc)
                 cj2_u = u_aug = u_mix
@@ -423,9 +357,7 @@ class ArcoStep2D(LossScaleGuard):
             # made its own: the momentum updates then land in the reference's order l, cj2_l, u (:310-312).
             t_side = None
             if TEACHER_SIDE:      # the teacher's grouped pass (independent of the student's) on a second stream, beside the student forward
-                if self._t_stream is None:
-                    self._t_stream = torch.cuda.Stream()
-                t_side = self._t_stream
+                t_side = self._stream("_t_stream")
                 t_side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(t_side), torch.no_grad(), ops.bn_groups(2), self._fm_t():
                     pred_t, _, fm_t = self.t_fwd_lu(lu)
@@ -478,9 +410,7 @@ class ArcoStep2D(LossScaleGuard):
                 ops.apply_deferred_bn(1)                                 # cj2_l (ran beside the teacher's first pass), then
                 ops.apply_deferred_bn()                                  # the u half / pass
             elif TEACHER_SIDE >= 2 and batched:    # (mode 2: this statistics-only pass too runs beside the main stream's work)
-                if self._t_stream is None:
-                    self._t_stream = torch.cuda.Stream()
-                self._t_stream.wait_stream(torch.cuda.current_stream())     # behind the student pass: BN buffers in the reference's order
+                self._stream("_t_stream").wait_stream(torch.cuda.current_stream())     # behind the student pass: BN buffers in the reference's order
                 with torch.cuda.stream(self._t_stream), self._fm_none():
                     self.s_fwd_stats(cj2_l)
                     ops.apply_deferred_bn()
@@ -552,15 +482,13 @@ class ArcoStep2D(LossScaleGuard):
             # the torch CPU generator, and the sampled indices must not depend on whether this term is on.
             nb2 = int(l_data.shape[0]) + int(u_aug.shape[0])
             if self.tps is None or self.tps.batch_size != nb2:
-                self.tps = RandTPS(a.patch_size[0], a.patch_size[1], batch_size=nb2, sigma=a.tps_sigma,
-                                   border_padding=False, random_mirror=True, random_scale=(0.8, 1.2), mode='affine',
-                                   device=l_data.device)                 # :255-261 (draws one warp, like the reference)
+                self.tps = self._make_tps(nb2, l_data.device)            # :255-261 (draws one warp, like the reference)
             eq_mask, images_cj2, pred_all_d = eqv_in
             with self._fm_none():          # (the mode the warped pass is captured under: GraphedTrain replays under no other)
                 tps_on_side = self._tps_side and self.s_train_tps.will_replay(images_cj2)
             tps_early = tps_on_side and TEACHER_SIDE >= 4
-            if tps_on_side and self._t_stream is None:
-                self._t_stream = torch.cuda.Stream()
+            if tps_on_side:
+                self._stream("_t_stream")
             if tps_early:
                 # Mode 4: the warps and the warped pass do not queue behind the main stream's row lists / bank appends / index
                 # uploads: they run on the side stream from the moment the host has drawn the warp, behind `eqv_in` on the main
@@ -627,9 +555,11 @@ class ArcoStep2D(LossScaleGuard):
             loss_q = glue.get_revisiting_loss(self.random_pool, rep_all[nb_l:], rep_all_teacher[nb_l:], topk=a.topk)
             glue.revisit_enqueue(rep_all_teacher[nb_l:], self.random_pool)
             ws.append(a.k4); terms.append(loss_q)
-        loss = ops.combine_terms(ws, terms)
-        self.optimizer.zero_grad()                                       # :429-431
-        if tps_on_side and SIDE_SYNC:
+        self._tps_on_side = tps_on_side
+        return self._step_tail(ws, terms, zero_path, loss_ce, loss_dice, unsup_loss, reco_loss, loss_eqv, loss_q)
+
+    def _before_backward(self):
+        if self._tps_on_side and SIDE_SYNC:
             # Round 4 shipped this host-side wait as a workaround: without it 1-3 % of steps had a gradient off by 1e-3..1e-2.  Round 5
             # found the cause - with the host ahead of the GPU the row-sparse head's backward runs BESIDE the warped pass's backward
             # graph (the overlap this schedule wants), and one packed-fp32 instruction the compiler had put into
@@ -638,37 +568,23 @@ class ArcoStep2D(LossScaleGuard):
             # The wait only removed the overlap at that point.  The kernel no longer contains the form; 0 of 1200 amplified trials
             # without the wait against 43 of 400 with the old code object on the same box (profiles/r05_notes.md section 1).
             self._t_stream.synchronize()
-        loss.backward()
-        ops.join_side()                     # weight gradients queued on the side stream (ops._wgrad)
-        if tps_on_side:
+
+    def _after_backward(self):
+        if self._tps_on_side:
             # the warped pass's backward graph was replayed on the side stream and hands nothing back to autograd (its parameter
             # gradients go straight into the second buffer), so the engine has no leaf stream to synchronise with at the end of
             # backward(): wait for it here.  (Found as a 1-in-3 flake of test_cfg2_graph_replay_equals_eager_at_full_size: the LAST
             # gradient of that backward, the first layer's weight, was merged before it was complete.)
             torch.cuda.current_stream().wait_stream(self._t_stream)
         self.optimizer.merge_second(self.heads_start)      # the warped pass's parameter gradients (replayed on the side stream)
-        if zero_path:     # `0 * rep.sum()` gives EVERY head parameter a zero gradient: SGD still decays / applies momentum to them
-            self.optimizer.touch_from(self.heads_start)
-        if ops.ACT_HALF:       # the U-Net's parameter gradients carry the loss scale of the f16 region
-            ok_unet = self._unscale_and_guard()
-        adist.allreduce_grads(self.optimizer)
-        if ops.ACT_HALF:
-            self._guard_heads_and_publish(ok_unet)
-        self.optimizer.step()
-        self.isd._momentum_update_key_encoder()                          # :432
-        lr_ = a.base_lr * (1.0 - self.iter_num / a.max_iterations) ** 0.9   # :433-435
-        for g in self.optimizer.param_groups:
-            g['lr'] = lr_
-        self.iter_num += 1
-        # values only: nothing returned or kept may hold this step's autograd graph alive into the next step
-        # (graphs.GraphedTrain needs the parameters' gradient accumulators recreated on its capture stream)
-        self.last_terms = dict(ce=loss_ce.detach(), dice=loss_dice.detach(), unsup=unsup_loss.detach(),
-                               reco=reco_loss.detach())
-        if loss_eqv is not None:
-            self.last_terms["eqv"] = loss_eqv.detach()
-        if loss_q is not None:
-            self.last_terms["loss_q"] = loss_q
-        return loss.detach(), reco_loss.detach()
+
+    def log_mode(self):
+        if ops.ACT_HALF and (self.iter_num == 1 or self.iter_num % 50 == 0 or self.iter_num == self.args.max_iterations):
+            logging.info('iteration %d : --act_dtype f16, loss scale %g, %d overflowed step(s) so far; %s'
+                         % (self.iter_num, ops.LOSS_SCALE, self.overflow_steps, self.fm_rows_note()))
+
+    def log_saved(self, path):
+        logging.info("save model to {}".format(path))
 
 
 def synthetic_batch(b, patch, n_cls, seed, device, in_chns=1):
@@ -690,8 +606,6 @@ def build_loaders(args, generator=None):
     patients_to_slices(exp, labeled_num) slices are the labeled stream, the rest the unlabeled one; RandomGenerator per
     sample; each loader draws with replacement and drops the last incomplete batch.  The Synapse / LiTS / JHU branches
     use the npz slice dataset with the reference's hard-wired list directories (--list_dir overrides them)."""
-    from torch.utils.data import ConcatDataset, DataLoader
-    from torch.utils.data.sampler import RandomSampler
     from .build_dataset import BaseDataSetsWithIndex, Synapse_datasetWithIndex
     from .dataloaders import Compose
     from .dataloaders.dataset import RandomGenerator
@@ -712,93 +626,15 @@ def build_loaders(args, generator=None):
     else:
         sets = [BaseDataSetsWithIndex(base_dir=args.root_path, split="train", num=None, transform=tf(), index=n_lab, label_type=t)
                 for t in (1, 0)]
-    db_l, db_u = sets
-    while len(db_l) < len(db_u):                                           # :196-197
-        db_l = ConcatDataset([db_l, db_l])
-    mk = lambda ds: DataLoader(ds, batch_size=args.batch_size, sampler=RandomSampler(data_source=ds, replacement=True, generator=generator),
-                               drop_last=True, pin_memory=True)
-    return mk(db_l), mk(db_u)
+    return stepper.paired_loaders(*sets, args.batch_size, generator)           # :196-215
 
 
 def train(args, snapshot_path):
-    rank, world = adist.init()
-    if getattr(args, "dp_local_thresholds", 0):
-        glue.state_reduce_hook = None
-    dev = torch.device("cuda", adist.local_rank())
-    torch.cuda.set_device(dev)
-    stepper = ArcoStep2D(args, dev)
-    b = args.batch_size
-    loaders = None
-    if args.synthetic:
-        iters_per_epoch = 100
-        if world > 1:         # every rank draws its own cutmix boxes / sampler indices / warps (seed + rank), after the broadcast
-            adist.seed_data_pipeline(args.seed)
-    else:
-        # data parallel: every rank draws its own samples / augmentations (seed + rank), after the weight broadcast above
-        loaders = build_loaders(args, generator=adist.seed_data_pipeline(args.seed) if world > 1 else None)
-        iters_per_epoch = len(loaders[1])                              # :217 iterations per epoch = unlabeled batches
-        logging.info("{} iterations per epoch".format(iters_per_epoch))
-        resume = "../model/{}_{}_labeledfinal/{}/iter_30000.pth".format(args.resume, args.labeled_num, args.model)
-        if os.path.exists(resume):                                      # stage-1 weights (:222-225), when present
-            sd = torch.load(resume, map_location="cpu")
-            stepper.isd.model.load_state_dict(sd); stepper.isd.ema_model.load_state_dict(sd)
-            for pl in stepper.plans:                                    # packed weights are stale now
-                pl.valid = False
-        else:
-            logging.info("no stage-1 checkpoint at {}: training from the random initialisation".format(resume))
-    max_epoch = args.max_iterations // iters_per_epoch + 1
-    l_iter = u_iter = None
-    while stepper.iter_num < args.max_iterations:
-        it = stepper.iter_num
-        if args.synthetic:
-            l_img, l_lab = synthetic_batch(b, args.patch_size, args.num_classes, 2 * it * world + rank, dev)
-            u_img, _ = synthetic_batch(b, args.patch_size, args.num_classes, (2 * it + 1) * world + rank, dev)
-        else:
-            if it % iters_per_epoch == 0:                               # :268-270 fresh iterators every epoch
-                l_iter, u_iter = iter(loaders[0]), iter(loaders[1])
-            l_next, u_next = next(l_iter), next(u_iter)
-            l_img, l_lab = l_next['image'].to(dev, non_blocking=True), l_next['label'].to(dev, non_blocking=True).long()
-            u_img = u_next['image'].to(dev, non_blocking=True)
-        loss, reco = stepper.step(l_img, l_lab, u_img, it // iters_per_epoch, max_epoch)
-        if rank == 0 and ops.ACT_HALF and (stepper.iter_num == 1 or stepper.iter_num % 50 == 0 or stepper.iter_num == args.max_iterations):
-            logging.info('iteration %d : --act_dtype f16, loss scale %g, %d overflowed step(s) so far; %s'
-                         % (stepper.iter_num, ops.LOSS_SCALE, stepper.overflow_steps, stepper.fm_rows_note()))
-        if rank == 0:
-            if "loss_q" in stepper.last_terms:                          # --revisit 1: the reference's logged total (:426,457)
-                logging.info('iteration %d : loss : %f, reco_loss: %f' % (stepper.iter_num, loss.item(), reco.item()))
-            else:
-                # the reference's logged `loss` also carries k4*loss_q, the revisiting term (:126-136,334,425) - a constant w.r.t. every
-                # parameter (no gradient path: weights, banks and every other logged value are unaffected) that needs the dense
-                # 496-channel representations of both nets; by default it is NOT computed, and the log line says so instead of
-                # printing a total that silently differs from the reference's (--revisit 1 computes and adds it)
-                logging.info('iteration %d : loss : %f (without the gradient-free revisiting term k4*loss_q, k4 = %g: --revisit 1 adds it), '
-                             'reco_loss: %f' % (stepper.iter_num, loss.item(), args.k4, reco.item()))
-            if stepper.iter_num % 1000 == 0:                           # :462-470
-                path = os.path.join(snapshot_path, 'iter_' + str(stepper.iter_num) + '.pth')
-                # parameters are views into the optimiser's flat buffer: save private copies, not the shared storage
-                torch.save({k: v.detach().clone() for k, v in stepper.isd.model.state_dict().items()}, path)
-                logging.info("save model to {}".format(path))
-    return "Training Finished!"
+    return stepper.train(args, snapshot_path, ArcoStep2D, synthetic_batch, build_loaders)
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    torch.set_num_threads(min(4, torch.get_num_threads()))   # host logic only; avoids OpenMP oversubscription stalls
-    random.seed(args.seed)                                               # :505-508
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    torch.cuda.manual_seed(args.seed)
-    snapshot_path = "../model/{}_{}_labeled{}/{}".format(args.exp, args.labeled_num, 'final', args.model)
-    try:                                                             # the reference writes next to the repo (../model)
-        os.makedirs(snapshot_path, exist_ok=True)
-    except OSError:                                                  # read-only parent: keep the run inside the cwd
-        snapshot_path = snapshot_path[1:]
-        os.makedirs(snapshot_path, exist_ok=True)
-    logging.basicConfig(filename=snapshot_path + "/log.txt", level=logging.INFO,
-                        format='[%(asctime)s.%(msecs)03d] %(message)s', datefmt='%H:%M:%S')
-    logging.getLogger().addHandler(logging.StreamHandler(sys.stdout))
-    logging.info(str(args))
-    return train(args, snapshot_path)
+    return stepper.main(argv, build_parser, train)
 
 
 if __name__ == "__main__":

@@ -9,10 +9,7 @@ SGD-Nesterov, EMA.  batch_transform is the identity in the reference's 3-D pipel
 --synthetic 0 trains from an LA dataset directory (build_loaders); --conv_mma selects reduced-precision MFMA operands.
 """
 import contextlib
-import logging
 import os
-import random
-import sys
 
 import numpy as np
 import torch
@@ -20,8 +17,8 @@ import torch.nn as nn
 
 from . import _contrast as C_
 from . import dist as adist
-from . import augment, glue, graphs, head, ops, optim
-from .loss_scale import LossScaleGuard
+from . import augment, glue, graphs, head, ops, stepper
+from .stepper import ArcoStepBase
 from .tps.rand_tps_3d import RandTPS as RandTPS3D
 from .model_3D import ISD_3d, FeatureExtractor_3d
 from .train_arco_2d import build_parser as _build_parser_2d
@@ -77,25 +74,20 @@ def _lowres(fe, fm):
     return lo, maps, [f.weight for f in (fe.fea2, fe.fea3, fe.fea4)[HEAD_LEVELS != 3:]]
 
 
-class ArcoStep3D(LossScaleGuard):
+class ArcoStep3D(ArcoStepBase):
     """State + one training step of the 3-D hot path (train_arco_3d.py:144-151,195-232,257-415)."""
 
     def __init__(self, args, device="cuda"):
         self.args = args
         self.dev = torch.device(device)
-        C = args.num_classes
-        ops.CONV_MMA = {"f32": 0, "f16": 1, "bf16": 2, "f32x3": 3}[getattr(args, "conv_mma", "f32x3")]
-        ops.ACT_HALF = getattr(args, "act_dtype", "f32") == "f16"          # before the PackPlans: they carry the f16 packs
-        hm = getattr(args, "head_mma", "auto")
-        ops.HEAD_MMA = {"auto": 1 if ops.ACT_HALF else 0, "f32x3": 0, "f16": 1, "bf16": 2}[hm]
-        ops.LOSS_SCALE = float(getattr(args, "loss_scale", 16384.0))
-        self.memobank, self.queue_ptrlis, self.queue_size = [], [], []
-        for i in range(C):                                                # :144-151
-            self.memobank.append([torch.randn(1, REP_DIM_3D)])
-            self.queue_size.append(args.queue_size if args.queue_size > 0 else 30000)
-            self.queue_ptrlis.append(torch.zeros(1, dtype=torch.long))
-        if args.queue_size <= 0:
-            self.queue_size[0] = 50000
+        half = getattr(args, "act_dtype", "f32") == "f16"
+        # weight gradients on the side stream behind their data gradient: -0.3 .. -0.5 ms on the LA step with round 6's 3x3x3 kernels
+        # (level on LiTS-f16; the 2-D step loses 1 ms with it and sets 0)
+        self._set_modes(conv_mma={"f32": 0, "f16": 1, "bf16": 2, "f32x3": 3}[getattr(args, "conv_mma", "f32x3")], act_half=half,
+                        head_mma={"auto": 1 if half else 0, "f32x3": 0, "f16": 1, "bf16": 2}[getattr(args, "head_mma", "auto")],
+                        wgrad_side=3)
+        # The torch CPU generator is consumed in the reference's order: banks (randn), pool, models, heads, one warp.
+        self._build_banks(lambda: torch.randn(1, REP_DIM_3D))             # :144-151
         self.random_pool = None
         if getattr(args, "revisit", 0):                                   # :153-156 (drawn right after the banks)
             args.dense_head = 1
@@ -104,81 +96,32 @@ class ArcoStep3D(LossScaleGuard):
         else:      # the pool's normals are not needed, its place in the CPU-generator sequence is (weight init, samplers, warps)
             from . import samplers
             samplers.skip_randn(args.K * REP_DIM_3D * int(np.prod(args.patch_size)))
-        self.isd = ISD_3d(K=args.K, m=0.99, Ts=0.01, Tt=0.1, num_classes=C,
+        self.isd = ISD_3d(K=args.K, m=0.99, Ts=0.01, Tt=0.1, num_classes=args.num_classes,
                           latent_pooling_size=args.latent_pooling_size, latent_feature_size=args.latent_feature_size,
                           output_pooling_size=args.output_pooling_size, train_encoder=True, train_decoder=True).to(self.dev)
-        self.model, self.ema_model = self.isd.model, self.isd.ema_model
-        self.q_representation = nn.Sequential(nn.Conv3d(REP_DIM_3D, REP_DIM_3D, kernel_size=1, bias=False),
-                                              nn.Conv3d(REP_DIM_3D, REP_DIM_3D, kernel_size=1, bias=False)).to(self.dev)
-        self.k_feature_extractor = FeatureExtractor_3d(fea_dim=FEA_DIM_3D, output_dim=REP_DIM_3D).to(self.dev)
-        self.q_feature_extractor = FeatureExtractor_3d(fea_dim=FEA_DIM_3D, output_dim=REP_DIM_3D).to(self.dev)
-        adist.broadcast_module_states([self.isd, self.q_representation, self.q_feature_extractor,
-                                       self.k_feature_extractor])
-        params = [p for p in self.model.parameters() if p.requires_grad]
-        params_rep = [p for p in self.q_representation.parameters() if p.requires_grad]
-        params_fea = [p for p in self.q_feature_extractor.parameters() if p.requires_grad]
-        self.heads_start = sum(p.numel() for p in params)     # flat_g[heads_start:] = the heads' gradient bucket (dist.mark_heads_done)
-        self.optimizer = optim.SGDNesterov(params + params_rep + params_fea, lr=args.base_lr, weight_decay=0.0001,
-                                           momentum=0.9, nesterov=True)
-        with torch.no_grad():
-            for t, s in zip(self.k_feature_extractor.parameters(), self.q_feature_extractor.parameters()):
-                t.data.copy_(s.data)
-                t.requires_grad = False
-        self.k_fe_ema = optim.EmaPair(self.q_feature_extractor, self.k_feature_extractor)
-        for m in (self.model, self.ema_model, self.q_representation, self.k_feature_extractor,
-                  self.q_feature_extractor):
-            m.train()
-        # packed conv weights: one launch per weight owner per step (ops.PackPlan), refreshed by the owner
-        plan_s = ops.PackPlan([self.model, self.q_representation, self.q_feature_extractor], True, half=[ops.ACT_HALF, False, False])
-        self.optimizer.plans = [plan_s]
-        pairs = self.isd._ensure_ema_pairs()
-        pairs[0].plans = [ops.PackPlan([self.ema_model], False, half=[ops.ACT_HALF])]
-        for pr in pairs[1:]:
-            pr.plans = [ops.PackPlan([], False)]
-        self.k_fe_ema.plans = [ops.PackPlan([self.k_feature_extractor], False)]
-        self.plans = [plan_s] + [pl for pr in pairs for pl in pr.plans] + self.k_fe_ema.plans
-        self.iter_num = 0
-        self._side, self._tps_pending = None, False
-        if ops._WGRAD_SIDE_ENV is None:        # weight gradients on the side stream behind their data gradient: -0.3 .. -0.5 ms on the LA step with
-            ops.WGRAD_SIDE = 3                 # round 6's 3x3x3 kernels (level on LiTS-f16; the 2-D step loses 1 ms with it: train_arco_2d resets it)
-        self._ovf_host, self._ovf_event, self.overflow_steps, self._clean_steps = None, None, 0, 0     # f16 overflow guard
-        self.keep_debug = False          # tests: keep the last step's plan and anchor rows (self.debug)
-        use_graphs = bool(getattr(args, "graphs", 1))
-        g_train = use_graphs and bool(getattr(args, "graph_train", 0))
-        self.s_train_u = graphs.GraphedTrain(self.model, enabled=g_train)    # student passes: fwd + bwd graphs
-        self.s_train_l = graphs.GraphedTrain(self.model, enabled=g_train)
-        self.tps = None
-        if getattr(args, "eqv_pass", 1):                                 # :231-237 (the constructor draws one warp)
-            self.tps = RandTPS3D(args.patch_size[0], args.patch_size[1], args.patch_size[2], batch_size=2 * args.batch_size,
-                                 sigma=args.tps_sigma, border_padding=False, random_mirror=True, random_scale=(0.8, 1.2),
-                                 mode='affine', device=device)
-        self.batched_passes = bool(getattr(args, "batched_passes", 1))
-        self.s_train_lu = graphs.GraphedTrain(self.model, enabled=g_train)
-        self.t_fwd_lu = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
-        self.t_fwd_u0 = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
+        self._build_heads(nn.Conv3d, FeatureExtractor_3d, FEA_DIM_3D, REP_DIM_3D)
+        self.tps = self._make_tps(2 * args.batch_size, device) if getattr(args, "eqv_pass", 1) else None    # :231-237
+        self._side, self._tps_pending = None, False      # side stream, created on first use (self._stream)
+        use_graphs, _ = self._build_graphs()
         self.t_fwd_ulu = graphs.GraphedForward(self.ema_model, enabled=use_graphs)      # T_MERGE: (u, l, u_aug) as one three-group pass
-        self.t_fwd_l = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
-        self.t_fwd_u = graphs.GraphedForward(self.ema_model, enabled=use_graphs)
         # the warped student pass carries no gradient after iteration 0 (:390-393): replayed as one graph - its ~300 eager
         # launches sat right behind the sampler stage, the stretch of the step where the GPU waits for the host
         self.s_fwd_tps = graphs.GraphedForward(self.model, enabled=use_graphs)
+
+    def _make_tps(self, batch_size, device):
+        """:231-237 (the constructor of RandTPS draws one warp, like the reference)."""
+        a = self.args
+        return RandTPS3D(a.patch_size[0], a.patch_size[1], a.patch_size[2], batch_size=batch_size, sigma=a.tps_sigma,
+                         border_padding=False, random_mirror=True, random_scale=(0.8, 1.2), mode='affine', device=device)
 
     @staticmethod
     def _lazy_teacher(kfe, fm_t):
         return head.LazyTeacher(*_lowres(kfe, fm_t))
 
-    def q_rep(self, x):
-        x = ops.conv(x, self.q_representation[0].weight)
-        return ops.conv(x, self.q_representation[1].weight)
-
     def step(self, l_data, l_label, u_data, epoch_num=0, max_epoch=1):
         a = self.args
         C = a.num_classes
-        if ops.ACT_HALF:
-            self._loss_scale_update()
-        for pl in self.plans:                                            # stale only if someone else touched weights
-            if not pl.valid:
-                pl.refresh()
+        self._step_head()
         # f16 activation storage with the row-sparse heads: the two full-resolution feature maps are consumed as stored (f16 rows,
         # f16 row-sparse gradients) - no dense cast of a full-resolution map in either direction (ops.fm_rows_half)
         rows_half = ops.ACT_HALF and FM_ROWS_HALF and not getattr(a, "dense_head", 0) and self.random_pool is None
@@ -192,15 +135,12 @@ class ArcoStep3D(LossScaleGuard):
                    and l_data.shape == u_data.shape)
         t_merge = bool(u0_side and T_MERGE)
         if t_merge:
-            if self._side is None:
-                self._side = torch.cuda.Stream()
+            self._stream("_side")
             mix_desc = augment.draw_boxes(int(u_data.shape[0]), tuple(int(v) for v in u_data.shape[2:]))
             u_aug = augment.mix_images(u_data, a.apply_aug, mix_desc)
         elif u0_side:
-            if self._side is None:
-                self._side = torch.cuda.Stream()
             mix_desc = augment.draw_boxes(int(u_data.shape[0]), tuple(int(v) for v in u_data.shape[2:]))
-            self._side.wait_stream(torch.cuda.current_stream())
+            self._stream("_side").wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._side), torch.no_grad(), ops.logits_only():      # :260-262
                 pred_u0, _, _ = self.t_fwd_u0(u_data)
                 pseudo_logits, pseudo_labels = glue.softmax_max(pred_u0)
@@ -221,9 +161,7 @@ class ArcoStep3D(LossScaleGuard):
             nb_l = int(l_data.shape[0])
             t_side = None
             if PASS_SIDE >= 1:      # the teacher's grouped pass on a second stream, beside the student forward (see train_arco_2d.TEACHER_SIDE)
-                if self._side is None:
-                    self._side = torch.cuda.Stream()
-                t_side = self._side
+                t_side = self._stream("_side")
                 t_side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(t_side), torch.no_grad():
                     if t_merge:
@@ -327,9 +265,7 @@ class ArcoStep3D(LossScaleGuard):
             # :368-388.  The warp is drawn after the samplers (same torch-generator order as the reference).
             nb2 = int(l_data.shape[0]) + int(u_aug.shape[0])
             if self.tps is None or self.tps.batch_size != nb2:
-                self.tps = RandTPS3D(a.patch_size[0], a.patch_size[1], a.patch_size[2], batch_size=nb2, sigma=a.tps_sigma,
-                                     border_padding=False, random_mirror=True, random_scale=(0.8, 1.2), mode='affine',
-                                     device=l_data.device)
+                self.tps = self._make_tps(nb2, l_data.device)
 
             def warp_inputs():
                 with torch.no_grad():
@@ -339,8 +275,8 @@ class ArcoStep3D(LossScaleGuard):
                     return (self.tps(torch.cat((l_data, u_aug))), self.tps(eq_mask, padding_mode='zeros'),
                             self.tps(torch.cat((pred_l.detach(), pred_u.detach())), padding_mode='zeros'))
             side_ok = PASS_SIDE >= 2 and self.iter_num > 0 and self.s_fwd_tps.enabled
-            if side_ok and self._side is None:
-                self._side = torch.cuda.Stream()
+            if side_ok:
+                self._stream("_side")
             if tps_early:
                 # after iteration 0 the warped pass is a logged value and a running-statistics update (:390-393): nothing of this
                 # step waits for it.  Warps, pass and loss run on the second stream from the moment the host has drawn the warp -
@@ -391,33 +327,12 @@ class ArcoStep3D(LossScaleGuard):
             glue.revisit_enqueue(rep_all_teacher[nb_l:], self.random_pool)
             if not first:
                 ws.append(a.k4); terms.append(loss_q)
-        loss = ops.combine_terms(ws, terms)           # one launch (and one for its backward) instead of a chain of 0-d ops
-        self.optimizer.zero_grad()
-        loss.backward()
-        ops.join_side()                     # weight gradients queued on the side stream (ops._wgrad)
+        return self._step_tail(ws, terms, zero_path and not first, loss_ce, loss_dice, unsup_loss, reco_loss, loss_eqv, loss_q)
+
+    def _after_backward(self):
         if self._tps_pending:               # the warped pass on the second stream reads the weights the optimiser is about to change
             torch.cuda.current_stream().wait_stream(self._side)
             self._tps_pending = False
-        if zero_path and not first:      # `0 * rep.sum()` (loss_helper.py:588-595): zero gradients for every head parameter
-            self.optimizer.touch_from(self.heads_start)
-        if ops.ACT_HALF:       # the V-Net's parameter gradients carry the loss scale of the f16 region
-            ok_vnet = self._unscale_and_guard()
-        adist.allreduce_grads(self.optimizer)
-        if ops.ACT_HALF:
-            self._guard_heads_and_publish(ok_vnet)
-        self.optimizer.step()
-        self.isd._momentum_update_key_encoder()
-        lr_ = a.base_lr * (1.0 - self.iter_num / a.max_iterations) ** 0.9
-        for g in self.optimizer.param_groups:
-            g['lr'] = lr_
-        self.iter_num += 1
-        self.last_terms = dict(ce=loss_ce.detach(), dice=loss_dice.detach(), unsup=unsup_loss.detach(),
-                               reco=reco_loss.detach())
-        if loss_eqv is not None:
-            self.last_terms["eqv"] = loss_eqv.detach()
-        if loss_q is not None:
-            self.last_terms["loss_q"] = loss_q
-        return loss.detach(), reco_loss.detach()
 
 
 def synthetic_volume_batch(b, patch, n_cls, seed, device):
@@ -437,91 +352,20 @@ def synthetic_volume_batch(b, patch, n_cls, seed, device):
 def build_loaders(args, generator=None):
     """The two training loaders of train_arco_3d.py:158-190: LAHeartWithIndex (first --labeled_num cases labeled, the
     rest unlabeled) with RandomRotFlip -> RandomCrop(patch) -> ToTensor, drawn with replacement, last batch dropped."""
-    from torch.utils.data import ConcatDataset, DataLoader
-    from torch.utils.data.sampler import RandomSampler
     from .dataloaders import Compose
     from .dataloaders.la_heart import LAHeartWithIndex, RandomCrop, RandomRotFlip, ToTensor
     tf = lambda: Compose([RandomRotFlip(), RandomCrop(args.patch_size), ToTensor()])
     db_l = LAHeartWithIndex(base_dir=args.root_path, split="train", num=None, transform=tf(), index=args.labeled_num, label_type=1)
     db_u = LAHeartWithIndex(base_dir=args.root_path, split="train", num=None, transform=tf(), index=args.labeled_num, label_type=0)
-    while len(db_l) < len(db_u):                                           # :171-172
-        db_l = ConcatDataset([db_l, db_l])
-    mk = lambda ds: DataLoader(ds, batch_size=args.batch_size, sampler=RandomSampler(data_source=ds, replacement=True, generator=generator),
-                               drop_last=True, pin_memory=True)
-    return mk(db_l), mk(db_u)
+    return stepper.paired_loaders(db_l, db_u, args.batch_size, generator)      # :171-190
 
 
 def train(args, snapshot_path):
-    rank, world = adist.init()
-    if getattr(args, "dp_local_thresholds", 0):
-        glue.state_reduce_hook = None
-    dev = torch.device("cuda", adist.local_rank())
-    torch.cuda.set_device(dev)
-    stepper = ArcoStep3D(args, dev)
-    b = args.batch_size
-    loaders = None
-    if args.synthetic:
-        iters_per_epoch = 100
-        if world > 1:         # every rank draws its own cutmix boxes / sampler indices / warps (seed + rank), after the broadcast
-            adist.seed_data_pipeline(args.seed)
-    else:
-        # data parallel: every rank draws its own samples / augmentations (seed + rank), after the weight broadcast above
-        loaders = build_loaders(args, generator=adist.seed_data_pipeline(args.seed) if world > 1 else None)
-        iters_per_epoch = len(loaders[1])
-        logging.info("{} iterations per epoch".format(iters_per_epoch))
-        resume = "../model/{}_{}_labeledfinal/{}/iter_30000.pth".format(args.resume, args.labeled_num, args.model)
-        if os.path.exists(resume):                                      # stage-1 weights (:198-201), when present
-            sd = torch.load(resume, map_location="cpu")
-            stepper.isd.model.load_state_dict(sd); stepper.isd.ema_model.load_state_dict(sd)
-            for pl in stepper.plans:
-                pl.valid = False
-        else:
-            logging.info("no stage-1 checkpoint at {}: training from the random initialisation".format(resume))
-    max_epoch = args.max_iterations // iters_per_epoch + 1
-    l_iter = u_iter = None
-    while stepper.iter_num < args.max_iterations:
-        it = stepper.iter_num
-        if args.synthetic:
-            l_img, l_lab = synthetic_volume_batch(b, args.patch_size, args.num_classes, 2 * it * world + rank, dev)
-            u_img, _ = synthetic_volume_batch(b, args.patch_size, args.num_classes, (2 * it + 1) * world + rank, dev)
-        else:
-            if it % iters_per_epoch == 0:
-                l_iter, u_iter = iter(loaders[0]), iter(loaders[1])
-            l_next, u_next = next(l_iter), next(u_iter)
-            l_img, l_lab = l_next['image'].to(dev, non_blocking=True), l_next['label'].to(dev, non_blocking=True).long()
-            u_img = u_next['image'].to(dev, non_blocking=True)
-        loss, reco = stepper.step(l_img, l_lab, u_img, it // iters_per_epoch, max_epoch)
-        if rank == 0:
-            if getattr(args, "revisit", 0):
-                logging.info('iteration %d : loss : %f, reco_loss: %f' % (stepper.iter_num, loss.item(), reco.item()))
-            else:      # (see train_arco_2d.train: the gradient-free revisiting term of the reference's logged total is opt-in)
-                logging.info('iteration %d : loss : %f (without the gradient-free revisiting term k4*loss_q, k4 = %g: --revisit 1 adds it), '
-                             'reco_loss: %f' % (stepper.iter_num, loss.item(), args.k4, reco.item()))
-            if stepper.iter_num % 1000 == 0:                           # :441-449
-                path = os.path.join(snapshot_path, 'iter_' + str(stepper.iter_num) + '.pth')
-                # parameters are views into the optimiser's flat buffer: save private copies, not the shared storage
-                torch.save({k: v.detach().clone() for k, v in stepper.isd.model.state_dict().items()}, path)
-    return "Training Finished!"
+    return stepper.train(args, snapshot_path, ArcoStep3D, synthetic_volume_batch, build_loaders)
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    torch.set_num_threads(min(4, torch.get_num_threads()))
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    torch.cuda.manual_seed(args.seed)
-    snapshot_path = "../model/{}_{}_labeled{}/{}".format(args.exp, args.labeled_num, 'final', args.model)
-    try:                                                             # the reference writes next to the repo (../model)
-        os.makedirs(snapshot_path, exist_ok=True)
-    except OSError:                                                  # read-only parent: keep the run inside the cwd
-        snapshot_path = snapshot_path[1:]
-        os.makedirs(snapshot_path, exist_ok=True)
-    logging.basicConfig(filename=snapshot_path + "/log.txt", level=logging.INFO,
-                        format='[%(asctime)s.%(msecs)03d] %(message)s', datefmt='%H:%M:%S')
-    logging.getLogger().addHandler(logging.StreamHandler(sys.stdout))
-    logging.info(str(args))
-    return train(args, snapshot_path)
+    return stepper.main(argv, build_parser, train)
 
 
 if __name__ == "__main__":
