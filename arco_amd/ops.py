@@ -5,6 +5,8 @@ memory (rows of C floats per pixel); a channel slice of such a tensor is consume
 in place through its row stride.  PyTorch only allocates memory and chains the
 autograd graph - every arithmetic op below is a hand-written gfx950 kernel.
 """
+import contextlib
+import os
 import weakref
 
 import torch
@@ -23,9 +25,15 @@ WORK = None          # bench.py sets {"bytes": 0.0, "flop": 0.0, "launches": 0}:
 def _work(nbytes, flop=0.0, launches=1):
     if WORK is not None and not torch.cuda.is_current_stream_capturing():
         WORK["bytes"] += float(nbytes); WORK["flop"] += float(flop); WORK["launches"] += launches
+
+
+def _env_int(name, default):      # an A/B switch, read from the environment once at import
+    return int(os.environ.get(name, default))
+
+
 BN_GROUPS = 1         # see bn_groups()
-POOL_FUSE = int(__import__('os').environ.get('ARCO_POOL_FUSE', '1'))             # A/B switch: 0 = separate max-pool pass in the U-Net encoder
-CONV_MMA = int(__import__('os').environ.get('ARCO_CONV_MMA', '3'))          # MFMA mode of the convolutions / GEMMs (forward and data gradient; --conv_mma of the trainers):
+POOL_FUSE = _env_int('ARCO_POOL_FUSE', 1)             # A/B switch: 0 = separate max-pool pass in the U-Net encoder
+CONV_MMA = _env_int('ARCO_CONV_MMA', 3)          # MFMA mode of the convolutions / GEMMs (forward and data gradient; --conv_mma of the trainers):
                       # 3 (default, "f32x3"): fp32-accurate products on the bf16 matrix cores - every fp32 operand is split
                       #    exactly into three bf16 terms and six v_mfma_f32_16x16x32_bf16 replace eight v_mfma_f32_16x16x4_f32
                       #    (error per product <= 2^-23, the size of one fp32 rounding; csrc/igemm.hip, MMA = 3);
@@ -94,7 +102,7 @@ class bn_defer:
 
 
 def _defer_args(running_mean, running_var, co, G, momentum):
-    """(defer_from, deferred buffer or None) for the arco_bn_finalize call of one BN layer."""
+    """(defer_from, deferred buffer or None) for the finalize call of one BN layer (_finalize_bn)."""
     if BN_DEFER is None or running_mean is None or BN_DEFER[0] >= G:
         return 0, None
     g0, slot = BN_DEFER
@@ -496,6 +504,29 @@ def _half_pack(half, taps, ci):
     return bool(half) and not (ci == 1 or (taps == 9 and ci <= 4))
 
 
+@contextlib.contextmanager
+def _profiled(key, taps, m, n, k):
+    """`with _profiled(key, taps, m, n, k): <the launch>` - the entry of a [m x k] x [k x n] x taps launch in PROFILE[key] =
+    {n, flop, timed: [(ev0, ev1, flop, (taps, m, n, k))]} (read by bench.py): every launch is counted, every PROFILE_EVERY-th one
+    is bracketed by HIP events on the launch stream (an event pair per launch costs ~1.5 ms/step of stream bubbles at ~350 conv
+    launches per step).  Launches outside the records (PROFILE off, a graph capture) take _unprofiled: nothing is built for them."""
+    flop = 2.0 * taps * m * n * k
+    rec = PROFILE.setdefault(key, {"n": 0, "flop": 0.0, "timed": []})
+    rec["n"] += 1
+    rec["flop"] += flop
+    ev = None
+    if rec["n"] % PROFILE_EVERY == 1 % PROFILE_EVERY:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    yield
+    if ev is not None:
+        ev[1].record()
+        rec["timed"].append((ev[0], ev[1], flop, (taps, m, n, k)))
+
+
+_unprofiled = contextlib.nullcontext()
+
+
 def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=0, stats=False, d3=1, sp=None,
              stat_groups=1, grad=False, half=False, pro=None, out=None, pro_groups=1):
     """out[pix][0..n) = conv(x)(+bias)(+residual); returns (out channels-last, stat slabs or None).
@@ -550,36 +581,26 @@ def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=
         esz = 2 if half else 4
         mpix = nb * d3 * h * w
         _work(mpix * (k + n) * esz + taps * n * k * 4 + (mpix * n * esz if residual is not None else 0), 2.0 * taps * mpix * n * k)
-    prof = cfg = None
+    key = None
     if PROFILE is not None and not image_h and not torch.cuda.is_current_stream_capturing():
-        # every launch is counted; every PROFILE_EVERY-th one is bracketed by HIP events on the launch stream
-        # (an event pair per launch costs ~1.5 ms/step of stream bubbles at ~350 conv launches per step)
-        key = (taps, nb * d3, h, w, k, n, ld, mma)
-        cfg = _cfg_cache.get(key)
-        if cfg is None:        # kernel instantiation id + 1e8 * matrix-core mode
-            cfg = _cfg_cache[key] = L.query("arco_conv_config_mma", *key) + 100000000 * mma
+        ck = (taps, nb * d3, h, w, k, n, ld, mma)
+        key = _cfg_cache.get(ck)
+        if key is None:        # kernel instantiation id + 1e8 * matrix-core mode
+            key = _cfg_cache[ck] = L.query("arco_conv_config_mma", *ck) + 100000000 * mma
         if pro is not None:
-            cfg += 50000000          # the PRO instantiation (consumer-side activation in the loader) is a kernel of its own in the records
-        rec = PROFILE.setdefault(cfg, {"n": 0, "flop": 0.0, "timed": []})
-        rec["n"] += 1
-        rec["flop"] += 2.0 * taps * nb * d3 * h * w * n * k
-        if rec["n"] % PROFILE_EVERY == 1 % PROFILE_EVERY:
-            prof = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            prof[0].record()
-    if image_h:
-        L.call("arco_conv3x3_image_fwd_h", L.ptr(xr), ld, k, L.ptr(wp), n, L.ptr(outr), ld_out, L.ptr(bias), L.ptr(ssum), L.ptr(ssq),
-               nb, h, w, stat_groups if stats else 1)
-    elif pro is not None:
-        if mma != 3:
-            raise RuntimeError("arco_amd: a consumer-side activation needs the split-bf16 kernels (ops.pro_ok)")
-        L.call("arco_conv3d_fwd_pro", L.ptr(xr), ld, k, L.ptr(wp), n, L.ptr(outr), ld_out, L.ptr(bias), L.ptr(residual), ld_res,
-               L.ptr(ssum), L.ptr(ssq), taps, nb, d3, h, w, stat_groups if stats else 1, mma, pro)
-    else:
-        L.call("arco_conv3d_fwd", L.ptr(xr), ld, k, L.ptr(wp), n, L.ptr(outr), ld_out, L.ptr(bias), L.ptr(residual), ld_res,
-               L.ptr(ssum), L.ptr(ssq), taps, nb, d3, h, w, stat_groups if stats else 1, mma)
-    if prof is not None:
-        prof[1].record()
-        PROFILE[cfg]["timed"].append((prof[0], prof[1], 2.0 * taps * nb * d3 * h * w * n * k, (taps, nb * d3 * h * w, n, k)))
+            key += 50000000          # the PRO instantiation (consumer-side activation in the loader) is a kernel of its own in the records
+    with _unprofiled if key is None else _profiled(key, taps, nb * d3 * h * w, n, k):
+        if image_h:
+            L.call("arco_conv3x3_image_fwd_h", L.ptr(xr), ld, k, L.ptr(wp), n, L.ptr(outr), ld_out, L.ptr(bias), L.ptr(ssum), L.ptr(ssq),
+                   nb, h, w, stat_groups if stats else 1)
+        elif pro is not None:
+            if mma != 3:
+                raise RuntimeError("arco_amd: a consumer-side activation needs the split-bf16 kernels (ops.pro_ok)")
+            L.call("arco_conv3d_fwd_pro", L.ptr(xr), ld, k, L.ptr(wp), n, L.ptr(outr), ld_out, L.ptr(bias), L.ptr(residual), ld_res,
+                   L.ptr(ssum), L.ptr(ssq), taps, nb, d3, h, w, stat_groups if stats else 1, mma, pro)
+        else:
+            L.call("arco_conv3d_fwd", L.ptr(xr), ld, k, L.ptr(wp), n, L.ptr(outr), ld_out, L.ptr(bias), L.ptr(residual), ld_res,
+                   L.ptr(ssum), L.ptr(ssq), taps, nb, d3, h, w, stat_groups if stats else 1, mma)
     return out, (ssum, ssq, nmb)
 
 
@@ -588,34 +609,23 @@ def conv_wgrad(dzr, ldz, co, xr, ldx, ci, taps, nb, h, w, like, d3=1, pro=None):
                      device=dzr.device)
 
     def compute(out, accumulate):
-        prof = None
-        if WORK is not None:
-            mpix = nb * d3 * h * w
-            _work(mpix * (co + ci) * (2 if _is_half(dzr) else 4) + taps * co * ci * 4, 2.0 * taps * mpix * co * ci, 2)      # + the slab reduction
-        if PROFILE is not None and not torch.cuda.is_current_stream_capturing():
-            flop = 2.0 * taps * nb * d3 * h * w * co * ci
-            rec = PROFILE.setdefault(("wgrad", taps, co, ci), {"n": 0, "flop": 0.0, "timed": []})
-            rec["n"] += 1
-            rec["flop"] += flop
-            if rec["n"] % PROFILE_EVERY == 1 % PROFILE_EVERY:
-                prof = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                prof[0].record()
+        mpix = nb * d3 * h * w
+        _work(mpix * (co + ci) * (2 if _is_half(dzr) else 4) + taps * co * ci * 4, 2.0 * taps * mpix * co * ci, 2)      # + the slab reduction
         if _is_half(dzr):     # f16 activation storage (xr is f16 too, or the first layer's fp32 one-channel volume)
             mma = 4
         else:
             mma = 3 if (CONV_MMA == 3 and taps in (9, 27)) else (2 if (CONV_MMA in (1, 2) and taps == 27) else 0)
-        if mma == 4 and taps == 9 and d3 == 1 and ci > 1 and not _is_half(xr):      # the U-Net's first layer on a 2- to 4-channel image:
-            # fp32 image x f16 gradient (a one-channel image takes the matrix-core kernel the V-Net's first layer uses, below: 38 vs 161 us)
-            L.call("arco_conv3x3_image_wgrad_h", L.ptr(dzr), ldz, co, L.ptr(xr), ldx, ci, nb, h, w, L.ptr(ws), L.ptr(out), accumulate)
-        elif pro is not None:
-            L.call("arco_conv3d_wgrad_pro", L.ptr(dzr), ldz, co, L.ptr(xr), ldx, ci, taps, nb, d3, h, w, L.ptr(ws), L.ptr(out),
-                   accumulate, mma, pro)
-        else:
-            L.call("arco_conv3d_wgrad", L.ptr(dzr), ldz, co, L.ptr(xr), ldx, ci, taps, nb, d3, h, w, L.ptr(ws), L.ptr(out),
-                   accumulate, mma)
-        if prof is not None:
-            prof[1].record()
-            rec["timed"].append((prof[0], prof[1], flop, (taps, nb * d3 * h * w, co, ci)))
+        key = ("wgrad", taps, co, ci) if PROFILE is not None and not torch.cuda.is_current_stream_capturing() else None
+        with _unprofiled if key is None else _profiled(key, taps, mpix, co, ci):      # (also while a side stream is current)
+            if mma == 4 and taps == 9 and d3 == 1 and ci > 1 and not _is_half(xr):      # the U-Net's first layer on a 2- to 4-channel image:
+                # fp32 image x f16 gradient (a one-channel image takes the matrix-core kernel the V-Net's first layer uses, below: 38 vs 161 us)
+                L.call("arco_conv3x3_image_wgrad_h", L.ptr(dzr), ldz, co, L.ptr(xr), ldx, ci, nb, h, w, L.ptr(ws), L.ptr(out), accumulate)
+            elif pro is not None:
+                L.call("arco_conv3d_wgrad_pro", L.ptr(dzr), ldz, co, L.ptr(xr), ldx, ci, taps, nb, d3, h, w, L.ptr(ws), L.ptr(out),
+                       accumulate, mma, pro)
+            else:
+                L.call("arco_conv3d_wgrad", L.ptr(dzr), ldz, co, L.ptr(xr), ldx, ci, taps, nb, d3, h, w, L.ptr(ws), L.ptr(out),
+                       accumulate, mma)
     return _grad_into(like, compute)
 
 
@@ -637,14 +647,13 @@ def conv_wgrad(dzr, ldz, co, xr, ldx, ci, taps, nb, h, w, like, d3=1, pro=None):
 # Round 6: with the pipelined 3x3x3 kernels the LA step gains 0.3-0.5 ms from mode 3 under graph replay (24.9 / 24.8 / 25.7 -> 24.6 / 24.4 / 25.2 ms,
 # same box, alternating; LiTS-f16 level, the 2-D step 11.0-11.2 -> 12.2-12.3): the 3-D trainer's constructor sets 3, the 2-D trainer's 0
 # (both through stepper.ArcoStepBase._set_modes, the one writer of the mode switches), unless ARCO_WGRAD_SIDE is given.
-_WGRAD_SIDE_ENV = __import__('os').environ.get('ARCO_WGRAD_SIDE')
-WGRAD_SIDE = int(_WGRAD_SIDE_ENV) if _WGRAD_SIDE_ENV is not None else 0
+_WGRAD_SIDE_ENV = os.environ.get('ARCO_WGRAD_SIDE')      # None when not given: the steppers then choose (stepper.ArcoStepBase._set_modes)
+WGRAD_SIDE = _env_int('ARCO_WGRAD_SIDE', 0)
 _side = {"stream": None, "keep": [], "dirty": False}
 
 
 def _wgrad(dzr, ldz, co, xr, ldx, ci, taps, nb, h, w, like, d3=1, keep=(), pro=None):
-    view = getattr(like, "_arco_grad_view", None)
-    if not (WGRAD_SIDE and view is not None and like.grad is not None and like.grad.data_ptr() == view.data_ptr()):
+    if not (WGRAD_SIDE and _flat_grad(like) is not None):
         return conv_wgrad(dzr, ldz, co, xr, ldx, ci, taps, nb, h, w, like, d3=d3, pro=pro)
     cur = torch.cuda.current_stream()
     if _side["stream"] is None:
@@ -683,13 +692,43 @@ def _zeros_cached(shape, device):
     return z
 
 
-def _grad_into(param, compute):
-    """Weight gradients go straight into the optimiser's flat gradient view when the parameter has one
-    (param._arco_grad_view, installed by optim.SGDNesterov): `compute(out, accumulate)` writes there with
-    accumulate=1 and autograd gets None - no per-parameter AccumulateGrad add kernel.  Otherwise the gradient
-    is returned normally."""
+def _flat_grad(param):
+    """The optimiser's flat gradient view of a parameter (param._arco_grad_view, installed by optim.SGDNesterov and
+    graphs.GraphedTrain) while param.grad still IS that view, else None.  Whoever writes a gradient into the view calls
+    param._arco_mark() - the optimiser steps marked parameters only - and hands autograd None."""
     view = getattr(param, "_arco_grad_view", None)
     if view is not None and param.grad is not None and param.grad.data_ptr() == view.data_ptr():
+        return view
+    return None
+
+
+def _affine_grad_targets(gamma, beta):
+    """(dg_t, db_t, acc, dgamma, dbeta): where a BatchNorm backward kernel writes its gamma / beta gradients and what autograd gets -
+    the flat views with accumulate = 1 and (None, None) when BOTH parameters are on the flat route (marked here), else fresh tensors."""
+    gv, bv = _flat_grad(gamma), _flat_grad(beta)
+    if gv is not None and bv is not None:
+        gamma._arco_mark(); beta._arco_mark()
+        return gv, bv, 1, None, None
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+    return dgamma, dbeta, 0, dgamma, dbeta
+
+
+def _zero_bias_grad(b, n, dev):
+    """The gradient of a conv bias under train-mode BatchNorm, analytically ZERO (BN removes the channel mean: sum(dz) =
+    -gamma*istd*mean(dy*xhat)*sum(xhat), sum(xhat) == 0; the reference's autograd produces fp32 rounding noise, ~1e-7), as exact
+    zeros without a column-sum pass: on the flat route `+= 0` launches nothing and the mark alone makes the optimiser step the bias."""
+    if _flat_grad(b) is not None:
+        b._arco_mark()
+        return None
+    return _zeros_cached((n,), dev)
+
+
+def _grad_into(param, compute):
+    """Weight gradients go straight into the optimiser's flat gradient view when the parameter has one (_flat_grad):
+    `compute(out, accumulate)` writes there with accumulate=1 and autograd gets None - no per-parameter AccumulateGrad
+    add kernel.  Otherwise the gradient is returned normally."""
+    view = _flat_grad(param)
+    if view is not None:
         compute(view, 1)
         param._arco_mark()
         return None
@@ -713,7 +752,7 @@ def colsum(xr, ld, m, c):
 # on those rows alone: the same kernels on [n, C] instead of [M, C] (data-gradient rows bit-identical - a row's result does not depend
 # on the other rows; weight gradients differ by fp32 summation order only), the rest of dx is a memset.  Needs the count on the host
 # (one synchronisation per layer): eager backward only, never inside a graph capture.  ARCO_SPARSE_BWD=0: always dense.
-SPARSE_BWD = int(__import__('os').environ.get('ARCO_SPARSE_BWD', '1'))
+SPARSE_BWD = _env_int('ARCO_SPARSE_BWD', 1)
 SPARSE_BWD_MIN_ROWS = 65536
 SPARSE_BWD_MIN_CH = 128          # the heads' widths (496 ... 384; 3-D 240 ... 128); the U-Net's own 1x1 convs stay below it
 SPARSE_BWD_MAX_FRAC = 0.125
@@ -858,24 +897,117 @@ def _bn_backward(da, z, mean, istd, gamma, beta, slope, drop_mode, p, seed, P, s
         dar = dar.to(zr.dtype)
         ldd = dar.stride(0)
     dz = new_act_nd(int(z.shape[0]), co, tuple(int(v) for v in z.shape[2:]), da.device, zr.dtype)
-    dgamma = dbeta = None
-    acc = 0
-    if gamma is not None:
-        gv, bv = getattr(gamma, "_arco_grad_view", None), getattr(beta, "_arco_grad_view", None)
-        if (gv is not None and bv is not None and gamma.grad is not None and beta.grad is not None
-                and gamma.grad.data_ptr() == gv.data_ptr() and beta.grad.data_ptr() == bv.data_ptr()):
-            dg_t, db_t, acc = gv, bv, 1               # straight into the optimiser's flat gradient buffer
-            gamma._arco_mark(); beta._arco_mark()
-        else:
-            dg_t = dgamma = torch.empty_like(gamma)
-            db_t = dbeta = torch.empty_like(beta)
-    else:
-        dg_t = db_t = None
+    dg_t, db_t, acc, dgamma, dbeta = _affine_grad_targets(gamma, beta) if gamma is not None else (None, None, 0, None, None)
     _work(5 * m * co * (2 if half else 4), 0.0, 3)     # reduce: dA, Z; apply: dA, Z -> dZ (algorithmic: dA, Z -> dZ would be 3)
     L.call("arco_bn_act_bwd_h" if half else "arco_bn_act_bwd", L.ptr(dar), ldd, L.ptr(zr), ldz, m, co, L.ptr(mean), L.ptr(istd),
            L.ptr(gamma), L.ptr(beta), slope, drop_mode, p, seed, P, L.ptr(ws), L.ptr(dg_t), L.ptr(db_t), acc, L.ptr(dz), co,
            L.ptr(seed_dev), groups)
     return dz, dgamma, dbeta
+
+
+def _bn_group_count(n):
+    """BN_GROUPS (see bn_groups) for a batch of n images / volumes."""
+    G = BN_GROUPS
+    if G > 1 and n % G != 0:
+        raise RuntimeError(f"arco_amd: bn_groups({G}) needs a batch that is a multiple of {G}, got {n}")
+    return G
+
+
+def _batch_stats(rows, ld, m, c, G):
+    """Per-channel partial sums of m rows of c channels in G groups of consecutive rows: (ssum, ssq [c][G * nblk], nblk)."""
+    nblk = L.query("arco_chan_stats_blocks", m // G)
+    ssum = torch.empty((c, G * nblk), dtype=torch.float32, device=rows.device)
+    ssq = torch.empty((c, G * nblk), dtype=torch.float32, device=rows.device)
+    L.call("arco_chan_stats_h" if _is_half(rows) else "arco_chan_stats", L.ptr(rows), ld, m, c, L.ptr(ssum), L.ptr(ssq), G)
+    return ssum, ssq, nblk
+
+
+def _finalize_bn(ssum, ssq, nmb, co, m, eps, momentum, running_mean, running_var, nbt, G, dev, counted=True):
+    """(mean, istd) [G][co] from the partial sums of the conv epilogue / _batch_stats, and the running-statistics update.
+    counted=False: the launch stays out of WORK (the finalize behind _batch_stats: BnActFn, BnActD2sFn)."""
+    mean = torch.empty(G * co, dtype=torch.float32, device=dev)      # [G][co]
+    istd = torch.empty(G * co, dtype=torch.float32, device=dev)
+    d0, dbuf = _defer_args(running_mean, running_var, co, G, momentum)
+    if counted:
+        _work(2 * co * nmb * 4)
+    L.call("arco_bn_finalize", L.ptr(ssum), L.ptr(ssq), nmb, co, m, float(eps), float(momentum), L.ptr(mean),
+           L.ptr(istd), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt), G, d0, L.ptr(dbuf))
+    return mean, istd
+
+
+_LAST_CAT_BUF = None
+
+
+def _act_out(nv, co, sp, dev, dtype, cat_room):
+    """(a, ld_a): a fresh activation [nv, co, *sp]; cat_room > 0: the leading channels of a buffer with that many more channels
+    (room for a later in-place channel concat, ops.upcat), the buffer left in _LAST_CAT_BUF for _take_cat_buf."""
+    global _LAST_CAT_BUF
+    if not cat_room:
+        return new_act_nd(nv, co, sp, dev, dtype), co
+    _LAST_CAT_BUF = new_act_nd(nv, co + int(cat_room), sp, dev, dtype)
+    return _LAST_CAT_BUF[:, :co], co + int(cat_room)
+
+
+def _take_cat_buf(y, pool):
+    """Hand the buffer _act_out left behind to the Function's result (attributes do not survive Function.apply)."""
+    global _LAST_CAT_BUF
+    (y[0] if pool else y)._arco_cat_buf, _LAST_CAT_BUF = _LAST_CAT_BUF, None
+
+
+def _bn_apply_pool(zr, ldz, nv, h, w, co, mean, istd, gamma, beta, slope, drop_mode, a, ld_a, G):
+    """The dropout-free apply pass of a 2-D stage into `a` AND a's 2x2 max-pool (encoder blocks: next DownBlock + decoder skip);
+    returns the pooled tensor.  fp32: one pass; f16 storage: the apply pass and the pooling pass (no pooled apply kernel in f16)."""
+    m = nv * h * w
+    pooled = new_act_nd(nv, co, (h // 2, w // 2), zr.device, zr.dtype)
+    if _is_half(zr):
+        _bn_apply(zr, ldz, m, co, mean, istd, gamma, beta, slope, drop_mode, 0.0, 0, h * w, a, ld_a, G)
+        _work((m + m // 4) * co * 2)
+        L.call("arco_maxpool2_fwd_h", L.ptr(a), ld_a, nv, h, w, co, L.ptr(pooled), co)
+    else:
+        _work((2 * m + m // 4) * co * 4)
+        L.call("arco_bn_act_pool_fwd", L.ptr(zr), ldz, nv, h, w, co, L.ptr(mean), L.ptr(istd), L.ptr(gamma), L.ptr(beta),
+               float(slope), L.ptr(a), ld_a, L.ptr(pooled), co, G)
+    return pooled
+
+
+def _stage_forward(xr, ld, ci, weight, bias, bn, geom, G, half=False, pro=None):
+    """One conv + train-mode BatchNorm stage up to its statistics: z = conv(x) + bias with the partial sums from the conv's
+    epilogue, then the finalize; returns (z, mean, istd).  bn = (running_mean, running_var, num_batches_tracked, momentum, eps),
+    geom = (taps, nv, d3, h, w, sp).  pro: xr is the producing stage's PRE-activation (see conv_raw)."""
+    taps, nv, d3, h, w, sp = geom
+    running_mean, running_var, nbt, momentum, eps = bn
+    co = int(weight.shape[0])
+    wp = pack_weight(weight, taps, 0, half=_half_pack(half, taps, ci))
+    z, (ssum, ssq, nmb) = conv_raw(xr, ld, ci, wp, co, nv, h, w, taps, bias=bias, stats=True, d3=d3, sp=sp, stat_groups=G,
+                                   half=half, pro=pro, pro_groups=G)
+    mean, istd = _finalize_bn(ssum, ssq, nmb, co, nv * d3 * h * w, eps, momentum, running_mean, running_var, nbt, G, xr.device)
+    return z, mean, istd
+
+
+def _stage_backward(da, z, mean, istd, gamma, beta, act, weight, xr, ldx, ci, geom, need_dx, need_dw, keep, pro=None, order=None):
+    """The backward of one stage a = drop(lrelu(BN(conv(x)))): BatchNorm backward, weight gradient, data gradient; returns
+    (dx, dw, dgamma, dbeta).  act = (slope, drop_mode, p, seed, seed_dev, groups); xr: the rows the convolution read (with pro: the
+    producing stage's pre-activation); keep: what the side stream must hold besides dz.  order, a WGRAD_SIDE value (None: WGRAD_SIDE
+    itself): below 2 the weight gradient is issued first and runs beside this stage's data gradient; from 2 behind the data gradient
+    (beside the next stage's BatchNorm backward passes); at 3 the data gradient also waits for the side stream."""
+    taps, nv, d3, h, w, sp = geom
+    slope, drop_mode, p, seed, seed_dev, G = act
+    co = int(weight.shape[0])
+    order = WGRAD_SIDE if order is None else order
+    dz, dgamma, dbeta = _bn_backward(da, z, mean, istd, gamma, beta, slope, drop_mode, p, seed, d3 * h * w, seed_dev, G)
+    dzr, ldz = rows_view(dz)
+    dx = dw = None
+    if need_dw and order < 2:
+        dw = _wgrad(dzr, ldz, co, xr, ldx, ci, taps, nv, h, w, weight, d3=d3, keep=(dz,) + keep, pro=pro)
+    if need_dx:
+        half = _is_half(dz)
+        wd = pack_weight(weight, taps, 1, half=half)
+        if order == 3 and _side["dirty"]:
+            torch.cuda.current_stream().wait_stream(_side["stream"])
+        dx, _ = conv_raw(dzr, ldz, co, wd, ci, nv, h, w, taps, d3=d3, sp=sp, grad=True, half=half)
+    if need_dw and order >= 2:
+        dw = _wgrad(dzr, ldz, co, xr, ldx, ci, taps, nv, h, w, weight, d3=d3, keep=(dz,) + keep, pro=pro)
+    return dx, dw, dgamma, dbeta
 
 
 class ConvBnActFn(torch.autograd.Function):
@@ -886,92 +1018,46 @@ class ConvBnActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, slope, p, drop_mode, momentum, eps,
                 nbt=None, cat_room=0, pool=False):
-        global _LAST_CAT_BUF
         L.require_gpu(x, weight)
         taps = _taps(weight)
         xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
         co = int(weight.shape[0])
-        m = nv * d3 * h * w
         half = use_half(x, taps, ci)
         _check_open_layer(half, xr, taps, d3, ci, co)
-        wp = pack_weight(weight, taps, 0, half=_half_pack(half, taps, ci))
-        G = BN_GROUPS
-        if G > 1 and nv % G != 0:
-            raise RuntimeError(f"arco_amd: bn_groups({G}) needs a batch that is a multiple of {G}, got {nv}")
-        z, (ssum, ssq, nmb) = conv_raw(xr, ld, ci, wp, co, nv, h, w, taps, bias=bias, stats=True, d3=d3, sp=sp,
-                                       stat_groups=G, half=half)
-        mean, istd = _finalize_bn(ssum, ssq, nmb, co, m, eps, momentum, running_mean, running_var, nbt, G, x.device)
+        G = _bn_group_count(nv)
+        z, mean, istd = _stage_forward(xr, ld, ci, weight, bias, (running_mean, running_var, nbt, momentum, eps),
+                                       (taps, nv, d3, h, w, sp), G, half=half)
         seed = _next_seed() if p > 0 else 0
-        if cat_room:        # leave room behind the channels for a later in-place channel concat (ops.upcat)
-            buf = new_act_nd(nv, co + int(cat_room), sp, x.device, z.dtype)
-            a, ld_a = buf[:, :co], co + int(cat_room)
-            _LAST_CAT_BUF = buf
-        else:
-            a, ld_a = new_act_nd(nv, co, sp, x.device, z.dtype), co
+        a, ld_a = _act_out(nv, co, sp, x.device, z.dtype, cat_room)
         zr, ldz = rows_view(z)
-        ctx.pool = bool(pool)
-        ctx.groups = G
+        ctx.pool, ctx.groups = bool(pool), G
         ctx.cfg = (taps, float(slope), float(p), int(drop_mode), seed, bias is not None)
         ctx.bias_param = bias
-        if pool:            # the activation AND its 2x2 max-pool in one pass (encoder blocks: next DownBlock + decoder skip)
+        if pool:            # the activation AND its 2x2 max-pool (_bn_apply_pool)
             if p > 0 or d3 != 1:
                 raise RuntimeError("arco_amd: conv_bn_act(pool=True) is the 2-D, dropout-free last stage of a ConvBlock")
-            pooled = new_act_nd(nv, co, (h // 2, w // 2), x.device, z.dtype)
-            if _is_half(zr):      # f16 storage: the apply pass and the pooling pass run separately (no pooled apply kernel in f16)
-                _bn_apply(zr, ldz, m, co, mean, istd, gamma, beta, slope, drop_mode, 0.0, 0, h * w, a, ld_a, G)
-                _work((m + m // 4) * co * 2)
-                L.call("arco_maxpool2_fwd_h", L.ptr(a), ld_a, nv, h, w, co, L.ptr(pooled), co)
-            else:
-                _work((2 * m + m // 4) * co * 4)
-                L.call("arco_bn_act_pool_fwd", L.ptr(zr), ldz, nv, h, w, co, L.ptr(mean), L.ptr(istd), L.ptr(gamma), L.ptr(beta),
-                       float(slope), L.ptr(a), ld_a, L.ptr(pooled), co, G)
+            pooled = _bn_apply_pool(zr, ldz, nv, h, w, co, mean, istd, gamma, beta, slope, drop_mode, a, ld_a, G)
             ctx.seed_dev = None
             ctx.set_materialize_grads(False)
             ctx.save_for_backward(x, weight, z, mean, istd, gamma, beta, a)
             return a, pooled
-        ctx.seed_dev = _bn_apply(zr, ldz, m, co, mean, istd, gamma, beta, slope, drop_mode, p, seed, d3 * h * w, a,
+        ctx.seed_dev = _bn_apply(zr, ldz, nv * d3 * h * w, co, mean, istd, gamma, beta, slope, drop_mode, p, seed, d3 * h * w, a,
                                  ld_a, G)
         ctx.save_for_backward(x, weight, z, mean, istd, gamma, beta)
         return a
 
     @staticmethod
     def backward(ctx, da, dpool=None):
-        if ctx.pool:
-            x, weight, z, mean, istd, gamma, beta, a = ctx.saved_tensors
-        else:
-            x, weight, z, mean, istd, gamma, beta = ctx.saved_tensors
+        x, weight, z, mean, istd, gamma, beta, *a = ctx.saved_tensors       # (a: the activation, saved on the pooled route only)
         taps, slope, p, drop_mode, seed, has_bias = ctx.cfg
         xr, ldx, nv, d3, h, w, ci, sp = _geom_nd(x)
         co = int(weight.shape[0])
         if ctx.pool and dpool is not None:       # d a = d skip + maxpool2_bwd(d pooled), summed inside the pooling backward
-            ar, lda_ = rows_view(a)
-            da = _maxpool2_backward(ar, lda_, nv, h, w, co, dpool, da)
-        dz, dgamma, dbeta = _bn_backward(da, z, mean, istd, gamma, beta, slope, drop_mode, p, seed, d3 * h * w,
-                                         ctx.seed_dev, ctx.groups)
-        dzr, ldzz = rows_view(dz)
-        dx = dw = db = None
-        # WGRAD_SIDE 1: the weight gradient forks first and runs beside this layer's data gradient; 2: it forks behind the data
-        # gradient (beside the next layer's BatchNorm backward passes); 3: as 2, and the next data gradient waits for it
-        if ctx.needs_input_grad[1] and WGRAD_SIDE < 2:
-            dw = _wgrad(dzr, ldzz, co, xr, ldx, ci, taps, nv, h, w, weight, d3=d3, keep=(dz, x))
-        if ctx.needs_input_grad[0]:
-            half = _is_half(dz)
-            wd = pack_weight(weight, taps, 1, half=half)
-            if WGRAD_SIDE == 3 and _side["dirty"]:
-                torch.cuda.current_stream().wait_stream(_side["stream"])
-            dx, _ = conv_raw(dzr, ldzz, co, wd, ci, nv, h, w, taps, d3=d3, sp=sp, grad=True, half=half)
-        if ctx.needs_input_grad[1] and WGRAD_SIDE >= 2:
-            dw = _wgrad(dzr, ldzz, co, xr, ldx, ci, taps, nv, h, w, weight, d3=d3, keep=(dz, x))
-        if has_bias and ctx.needs_input_grad[2]:
-            # a conv bias under train-mode BN has an analytically ZERO gradient (BN removes the channel mean):
-            # sum(dz) = -gamma*istd*mean(dy*xhat)*sum(xhat) and sum(xhat) == 0.  The reference's autograd
-            # produces fp32 rounding noise (~1e-7) here; we return exact zeros instead of a column-sum pass.
-            b = ctx.bias_param
-            view = getattr(b, "_arco_grad_view", None)
-            if view is not None and b.grad is not None and b.grad.data_ptr() == view.data_ptr():
-                b._arco_mark()          # += 0 into the flat gradient: nothing to launch, the optimiser still steps it
-            else:
-                db = _zeros_cached((co,), da.device)
+            da = _maxpool2_backward(*rows_view(a[0]), nv, h, w, co, dpool, da)
+        dx, dw, dgamma, dbeta = _stage_backward(da, z, mean, istd, gamma, beta, (slope, drop_mode, p, seed, ctx.seed_dev, ctx.groups),
+                                                weight, xr, ldx, ci, (taps, nv, d3, h, w, sp), ctx.needs_input_grad[0],
+                                                ctx.needs_input_grad[1], keep=(x,))
+        db = _zero_bias_grad(ctx.bias_param, co, x.device) if has_bias and ctx.needs_input_grad[2] else None
         return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None
 
 
@@ -983,24 +1069,18 @@ def conv_block3d_nograd(x, stages):
     the activation less per link.  stages: [(conv, bn), ...]; the caller has checked block3d_fusable."""
     L.require_gpu(x)
     xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
-    G = BN_GROUPS
-    if G > 1 and nv % G != 0:
-        raise RuntimeError(f"arco_amd: bn_groups({G}) needs a batch that is a multiple of {G}, got {nv}")
-    m = nv * d3 * h * w
+    G = _bn_group_count(nv)
     pro = None
     zr, ldz, k = xr, ld, ci
     for conv, bn in stages:
-        co = int(conv.weight.shape[0])
-        z, (ssum, ssq, nmb) = conv_raw(zr, ldz, k, pack_weight(conv.weight, 27, 0), co, nv, h, w, 27, bias=conv.bias, stats=True, d3=d3, sp=sp,
-                                       stat_groups=G, pro=pro, pro_groups=G)
-        mean, istd = _finalize_bn(ssum, ssq, nmb, co, m, bn.eps, bn.momentum, bn.running_mean, bn.running_var, bn.num_batches_tracked, G, x.device)
+        z, mean, istd = _stage_forward(zr, ldz, k, conv.weight, conv.bias,
+                                       (bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps),
+                                       (27, nv, d3, h, w, sp), G, pro=pro)
         zr, ldz = rows_view(z)
-        k = co
+        k = int(conv.weight.shape[0])
         pro = L.act_pro(mean, istd, bn.weight, bn.bias, 0.0, G, 0, 0.0, 0, None)
-        last = (z, mean, istd, bn, co)
-    z, mean, istd, bn, co = last
-    a = new_act_nd(nv, co, sp, x.device)
-    _bn_apply(zr, ldz, m, co, mean, istd, bn.weight, bn.bias, 0.0, 0, 0.0, 0, d3 * h * w, a, co, G)
+    a = new_act_nd(nv, k, sp, x.device)
+    _bn_apply(zr, ldz, nv * d3 * h * w, k, mean, istd, bn.weight, bn.bias, 0.0, 0, 0.0, 0, d3 * h * w, a, k, G)
     block_fuse_stats["fused3d"] = block_fuse_stats.get("fused3d", 0) + len(stages) - 1
     return a
 
@@ -1027,8 +1107,8 @@ def block3d_fusable(x, stages):
 
 # A/B switch of conv_block3d_nograd; OFF by default: measured level with the staged route (the loaders' prologue costs what the apply
 # pass of these small tensors costs: tools/micro/fl_pro_bench.py, profiles/r06_notes.md section 10; LA step 24.9-25.0 -> 25.1-25.2 ms)
-BLOCK_FUSE3D = int(__import__('os').environ.get('ARCO_BLOCK_FUSE3D', '0'))
-BLOCK_FUSE = int(__import__('os').environ.get('ARCO_BLOCK_FUSE', '1'))    # A/B switch: 0 = every stage writes its activation (rounds 1-5)
+BLOCK_FUSE3D = _env_int('ARCO_BLOCK_FUSE3D', 0)
+BLOCK_FUSE = _env_int('ARCO_BLOCK_FUSE', 1)    # A/B switch: 0 = every stage writes its activation (rounds 1-5)
 block_fuse_stats = {"fused": 0, "unfused": 0}       # how often conv_block took each route (tests, bench)
 
 
@@ -1042,16 +1122,6 @@ def pro_ok(taps, nv, d3, h, w, ci, co, ld, groups):
     return r
 
 
-def _finalize_bn(ssum, ssq, nmb, co, m, eps, momentum, running_mean, running_var, nbt, G, dev):
-    mean = torch.empty(G * co, dtype=torch.float32, device=dev)      # [G][co]
-    istd = torch.empty(G * co, dtype=torch.float32, device=dev)
-    d0, dbuf = _defer_args(running_mean, running_var, co, G, momentum)
-    _work(2 * co * nmb * 4)
-    L.call("arco_bn_finalize", L.ptr(ssum), L.ptr(ssq), nmb, co, m, float(eps), float(momentum), L.ptr(mean),
-           L.ptr(istd), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt), G, d0, L.ptr(dbuf))
-    return mean, istd
-
-
 class ConvBlockFn(torch.autograd.Function):
     """A whole ConvBlock of the U-Net (unetWithArgs.py:31-47: conv3x3 - BN - LeakyReLU - Dropout(p) - conv3x3 - BN - LeakyReLU) as ONE
     autograd node whose first stage never writes its activation: conv1 stores z1 (+ BN partial statistics), the statistics are
@@ -1063,111 +1133,69 @@ class ConvBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, g1, be1, rm1, rv1, nbt1, w2, b2, g2, be2, rm2, rv2, nbt2, slope1, p1, slope2, mom1, eps1, mom2, eps2,
                 cat_room=0, pool=False):
-        global _LAST_CAT_BUF
         L.require_gpu(x, w1, w2)
         xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
         cm, co = int(w1.shape[0]), int(w2.shape[0])
-        m = nv * h * w
-        G = BN_GROUPS
-        if G > 1 and nv % G != 0:
-            raise RuntimeError(f"arco_amd: bn_groups({G}) needs a batch that is a multiple of {G}, got {nv}")
-        dev = x.device
+        G = _bn_group_count(nv)
+        geom = (9, nv, 1, h, w, sp)
         # stage 1: z1 = conv1(x) + b1, statistics
-        z1, (s1, q1, nmb1) = conv_raw(xr, ld, ci, pack_weight(w1, 9, 0), cm, nv, h, w, 9, bias=b1, stats=True, stat_groups=G)
-        mean1, istd1 = _finalize_bn(s1, q1, nmb1, cm, m, eps1, mom1, rm1, rv1, nbt1, G, dev)
+        z1, mean1, istd1 = _stage_forward(xr, ld, ci, w1, b1, (rm1, rv1, nbt1, mom1, eps1), geom, G)
         seed1 = _next_seed() if p1 > 0 else 0
         seed_dev = SEED_DEV if (p1 > 0 and torch.cuda.is_current_stream_capturing()) else None
         z1r, ldz1 = rows_view(z1)
         pro = L.act_pro(mean1, istd1, g1, be1, slope1, G, 1 if p1 > 0 else 0, p1, seed1, seed_dev)
         # stage 2: z2 = conv2(act(z1)) + b2 with the activation applied in the loader
-        z2, (s2, q2, nmb2) = conv_raw(z1r, ldz1, cm, pack_weight(w2, 9, 0), co, nv, h, w, 9, bias=b2, stats=True, stat_groups=G, pro=pro)
-        mean2, istd2 = _finalize_bn(s2, q2, nmb2, co, m, eps2, mom2, rm2, rv2, nbt2, G, dev)
-        if cat_room:
-            buf = new_act_nd(nv, co + int(cat_room), sp, dev)
-            a, ld_a = buf[:, :co], co + int(cat_room)
-            _LAST_CAT_BUF = buf
-        else:
-            a, ld_a = new_act_nd(nv, co, sp, dev), co
+        z2, mean2, istd2 = _stage_forward(z1r, ldz1, cm, w2, b2, (rm2, rv2, nbt2, mom2, eps2), geom, G, pro=pro)
+        a, ld_a = _act_out(nv, co, sp, x.device, torch.float32, cat_room)
         z2r, ldz2 = rows_view(z2)
         ctx.pool, ctx.groups = bool(pool), G
         ctx.cfg = (float(slope1), float(p1), seed1, float(slope2))
         ctx.seed_dev = seed_dev
         ctx.params = (b1, b2)
         if pool:
-            pooled = new_act(nv, co, h // 2, w // 2, dev)
-            _work((2 * m + m // 4) * co * 4)
-            L.call("arco_bn_act_pool_fwd", L.ptr(z2r), ldz2, nv, h, w, co, L.ptr(mean2), L.ptr(istd2), L.ptr(g2), L.ptr(be2),
-                   float(slope2), L.ptr(a), ld_a, L.ptr(pooled), co, G)
+            pooled = _bn_apply_pool(z2r, ldz2, nv, h, w, co, mean2, istd2, g2, be2, slope2, 0, a, ld_a, G)
             ctx.set_materialize_grads(False)
             ctx.save_for_backward(x, w1, z1, mean1, istd1, g1, be1, w2, z2, mean2, istd2, g2, be2, a)
             return a, pooled
-        _bn_apply(z2r, ldz2, m, co, mean2, istd2, g2, be2, slope2, 0, 0.0, 0, h * w, a, ld_a, G)
+        _bn_apply(z2r, ldz2, nv * h * w, co, mean2, istd2, g2, be2, slope2, 0, 0.0, 0, h * w, a, ld_a, G)
         ctx.save_for_backward(x, w1, z1, mean1, istd1, g1, be1, w2, z2, mean2, istd2, g2, be2)
         return a
 
     @staticmethod
     def backward(ctx, da, dpool=None):
-        if ctx.pool:
-            x, w1, z1, mean1, istd1, g1, be1, w2, z2, mean2, istd2, g2, be2, a = ctx.saved_tensors
-        else:
-            x, w1, z1, mean1, istd1, g1, be1, w2, z2, mean2, istd2, g2, be2 = ctx.saved_tensors
+        x, w1, z1, mean1, istd1, g1, be1, w2, z2, mean2, istd2, g2, be2, *a = ctx.saved_tensors      # (a: on the pooled route only)
         slope1, p1, seed1, slope2 = ctx.cfg
         b1, b2 = ctx.params
         G = ctx.groups
+        need = ctx.needs_input_grad
         xr, ldx, nv, d3, h, w, ci, sp = _geom_nd(x)
         cm, co = int(w1.shape[0]), int(w2.shape[0])
-        dev = x.device
+        geom = (9, nv, 1, h, w, sp)
         if ctx.pool and dpool is not None:       # d a = d skip + maxpool2_bwd(d pooled), summed inside the pooling backward
-            ar, lda_ = rows_view(a)
-            dpr, ldp = rows_view(dpool)
-            dsum = new_act(nv, co, h, w, dev)
-            _work((nv * h * w * (3 if da is not None else 2) + nv * h * w // 4) * co * 4)
-            if da is None:
-                L.call("arco_maxpool2_bwd", L.ptr(ar), lda_, nv, h, w, co, L.ptr(dpr), ldp, L.ptr(dsum), co)
-            else:
-                sr, lds = rows_view(da)
-                L.call("arco_maxpool2_bwd_add", L.ptr(ar), lda_, nv, h, w, co, L.ptr(dpr), ldp, L.ptr(sr), lds, L.ptr(dsum), co)
-            da = dsum
-        # ---- stage 2
-        dz2, dg2, dbe2 = _bn_backward(da, z2, mean2, istd2, g2, be2, slope2, 0, 0.0, 0, h * w, None, G)
-        dz2r, lddz2 = rows_view(dz2)
+            da = _maxpool2_backward(*rows_view(a[0]), nv, h, w, co, dpool, da)
+        # ---- stage 2: its convolution read z1 through the consumer-side activation, and so does its weight gradient.  order=0 (both
+        # stages): the weight gradient goes first whatever WGRAD_SIDE says - with 2 / 3 unlike ConvBnActFn, an open inconsistency
         z1r, ldz1 = rows_view(z1)
-        dw2 = None
-        if ctx.needs_input_grad[8]:
-            pro = L.act_pro(mean1, istd1, g1, be1, slope1, G, 1 if p1 > 0 else 0, p1, seed1, ctx.seed_dev)
-            dw2 = _wgrad(dz2r, lddz2, co, z1r, ldz1, cm, 9, nv, h, w, w2, keep=(dz2, z1, mean1, istd1), pro=pro)
-        da1, _ = conv_raw(dz2r, lddz2, co, pack_weight(w2, 9, 1), cm, nv, h, w, 9, grad=True)
+        pro = L.act_pro(mean1, istd1, g1, be1, slope1, G, 1 if p1 > 0 else 0, p1, seed1, ctx.seed_dev) if need[8] else None
+        da1, dw2, dg2, dbe2 = _stage_backward(da, z2, mean2, istd2, g2, be2, (slope2, 0, 0.0, 0, None, G), w2, z1r, ldz1, cm, geom,
+                                              True, need[8], keep=(z1, mean1, istd1), pro=pro, order=0)
         # ---- stage 1 (its activation is recomputed from z1 inside the BatchNorm backward kernels)
-        dz1, dg1, dbe1 = _bn_backward(da1, z1, mean1, istd1, g1, be1, slope1, 1 if p1 > 0 else 0, p1, seed1, h * w, ctx.seed_dev, G)
-        dz1r, lddz1 = rows_view(dz1)
-        dw1 = dx = None
-        if ctx.needs_input_grad[1]:
-            dw1 = _wgrad(dz1r, lddz1, cm, xr, ldx, ci, 9, nv, h, w, w1, keep=(dz1, x))
-        if ctx.needs_input_grad[0]:
-            dx, _ = conv_raw(dz1r, lddz1, cm, pack_weight(w1, 9, 1), ci, nv, h, w, 9, grad=True)
-        # conv biases under train-mode BN: analytically zero gradients (see ConvBnActFn.backward)
-        dbs = []
-        for b, cn, need in ((b1, cm, ctx.needs_input_grad[2]), (b2, co, ctx.needs_input_grad[9])):
-            db = None
-            if b is not None and need:
-                view = getattr(b, "_arco_grad_view", None)
-                if view is not None and b.grad is not None and b.grad.data_ptr() == view.data_ptr():
-                    b._arco_mark()
-                else:
-                    db = _zeros_cached((cn,), dev)
-            dbs.append(db)
-        return (dx, dw1, dbs[0], dg1, dbe1, None, None, None, dw2, dbs[1], dg2, dbe2, None, None, None) + (None,) * 9
+        dx, dw1, dg1, dbe1 = _stage_backward(da1, z1, mean1, istd1, g1, be1, (slope1, 1 if p1 > 0 else 0, p1, seed1, ctx.seed_dev, G),
+                                             w1, xr, ldx, ci, geom, need[0], need[1], keep=(x,), order=0)
+        db1 = _zero_bias_grad(b1, cm, x.device) if b1 is not None and need[2] else None
+        db2 = _zero_bias_grad(b2, co, x.device) if b2 is not None and need[9] else None
+        return (dx, dw1, db1, dg1, dbe1, None, None, None, dw2, db2, dg2, dbe2, None, None, None) + (None,) * 9
 
 
 def conv_block(x, conv1, bn1, act1, p1, conv2, bn2, act2, cat_room=0, pool=False):
     """The train-mode ConvBlock: ConvBlockFn when both convolutions run on the pipelined kernels (ops.pro_ok), else None (the
     caller runs the two stages separately)."""
-    global _LAST_CAT_BUF
     if not BLOCK_FUSE or x.dim() != 4 or x.dtype != torch.float32 or use_half(x, 9, int(x.shape[1])):
         return None       # (f16 activation storage runs the two stages separately: no consumer-side activation in the f16 loaders)
     xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
     cm, co = int(conv1.weight.shape[0]), int(conv2.weight.shape[0])
-    if _taps(conv1.weight) != 9 or _taps(conv2.weight) != 9 or not pro_ok(9, nv, 1, h, w, cm, co, cm, BN_GROUPS):
+    G = _bn_group_count(nv)      # (before either counter moves)
+    if _taps(conv1.weight) != 9 or _taps(conv2.weight) != 9 or not pro_ok(9, nv, 1, h, w, cm, co, cm, G):
         block_fuse_stats["unfused"] += 1
         return None
     block_fuse_stats["fused"] += 1
@@ -1176,7 +1204,7 @@ def conv_block(x, conv1, bn1, act1, p1, conv2, bn2, act2, cat_room=0, pool=False
                           getattr(act1, "negative_slope", 0.0), float(p1), getattr(act2, "negative_slope", 0.0),
                           bn1.momentum, bn1.eps, bn2.momentum, bn2.eps, cat_room, pool)
     if cat_room:
-        (y[0] if pool else y)._arco_cat_buf, _LAST_CAT_BUF = _LAST_CAT_BUF, None
+        _take_cat_buf(y, pool)
     return y
 
 
@@ -1196,18 +1224,9 @@ class BnActFn(torch.autograd.Function):
         mean = istd = None
         G = 1
         if gamma is not None:
-            G = BN_GROUPS
-            if G > 1 and int(z.shape[0]) % G != 0:
-                raise RuntimeError(f"arco_amd: bn_groups({G}) needs a batch that is a multiple of {G}")
-            nblk = L.query("arco_chan_stats_blocks", m // G)
-            ssum = torch.empty((co, G * nblk), dtype=torch.float32, device=z.device)
-            ssq = torch.empty((co, G * nblk), dtype=torch.float32, device=z.device)
-            L.call("arco_chan_stats_h" if _is_half(zr) else "arco_chan_stats", L.ptr(zr), ldz, m, co, L.ptr(ssum), L.ptr(ssq), G)
-            mean = torch.empty(G * co, dtype=torch.float32, device=z.device)
-            istd = torch.empty(G * co, dtype=torch.float32, device=z.device)
-            d0, dbuf = _defer_args(running_mean, running_var, co, G, momentum)
-            L.call("arco_bn_finalize", L.ptr(ssum), L.ptr(ssq), G * nblk, co, m, float(eps), float(momentum), L.ptr(mean),
-                   L.ptr(istd), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt), G, d0, L.ptr(dbuf))
+            G = _bn_group_count(int(z.shape[0]))
+            ssum, ssq, nblk = _batch_stats(zr, ldz, m, co, G)
+            mean, istd = _finalize_bn(ssum, ssq, G * nblk, co, m, eps, momentum, running_mean, running_var, nbt, G, z.device, counted=False)
         seed = _next_seed() if p > 0 else 0
         a = new_act_nd(int(z.shape[0]), co, sp, z.device, zr.dtype)
         ctx.has_res = residual is not None
@@ -1251,18 +1270,9 @@ class BnActD2sFn(torch.autograd.Function):
             raise RuntimeError("arco_amd: bn_act_d2s needs a dense [N, 8C, X, Y, Z] channels-last tensor with C % 4 == 0")
         half = _is_half(yr)
         m8 = yr.shape[0] * 8
-        G = BN_GROUPS
-        if G > 1 and n % G != 0:
-            raise RuntimeError(f"arco_amd: bn_groups({G}) needs a batch that is a multiple of {G}")
-        nblk = L.query("arco_chan_stats_blocks", m8 // G)
-        ssum = torch.empty((c, G * nblk), dtype=torch.float32, device=y.device)
-        ssq = torch.empty((c, G * nblk), dtype=torch.float32, device=y.device)
-        L.call("arco_chan_stats_h" if half else "arco_chan_stats", L.ptr(yr), c, m8, c, L.ptr(ssum), L.ptr(ssq), G)
-        mean = torch.empty(G * c, dtype=torch.float32, device=y.device)
-        istd = torch.empty(G * c, dtype=torch.float32, device=y.device)
-        d0, dbuf = _defer_args(running_mean, running_var, c, G, momentum)
-        L.call("arco_bn_finalize", L.ptr(ssum), L.ptr(ssq), G * nblk, c, m8, float(eps), float(momentum), L.ptr(mean),
-               L.ptr(istd), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt), G, d0, L.ptr(dbuf))
+        G = _bn_group_count(n)
+        ssum, ssq, nblk = _batch_stats(yr, c, m8, c, G)      # (voxel, tap) rows of c channels
+        mean, istd = _finalize_bn(ssum, ssq, G * nblk, c, m8, eps, momentum, running_mean, running_var, nbt, G, y.device, counted=False)
         a = new_act_nd(n, c, (2 * x2, 2 * y2, 2 * z2), y.device, yr.dtype)
         rr, ldr = (None, 0)
         if residual is not None:
@@ -1290,16 +1300,7 @@ class BnActD2sFn(torch.autograd.Function):
             ldd = dar.stride(0)
         dy = new_act_nd(n, c8, (x2, y2, z2), y.device, yr.dtype)
         ws = torch.empty(G * (2 * c * nblk + 2 * c), dtype=torch.float32, device=y.device)
-        dgamma = dbeta = None
-        acc = 0
-        gv, bv = getattr(gamma, "_arco_grad_view", None), getattr(beta, "_arco_grad_view", None)
-        if (gv is not None and bv is not None and gamma.grad is not None and beta.grad is not None
-                and gamma.grad.data_ptr() == gv.data_ptr() and beta.grad.data_ptr() == bv.data_ptr()):
-            dg_t, db_t, acc = gv, bv, 1               # straight into the optimiser's flat gradient buffer
-            gamma._arco_mark(); beta._arco_mark()
-        else:
-            dg_t = dgamma = torch.empty_like(gamma)
-            db_t = dbeta = torch.empty_like(beta)
+        dg_t, db_t, acc, dgamma, dbeta = _affine_grad_targets(gamma, beta)
         L.call("arco_bn_act_d2s_bwd_h" if half else "arco_bn_act_d2s_bwd", L.ptr(dar), ldd, L.ptr(yr), yr.shape[0] * 8, c, L.ptr(mean),
                L.ptr(istd), L.ptr(gamma), L.ptr(beta), slope, L.ptr(ws), L.ptr(dg_t), L.ptr(db_t), acc, L.ptr(dy), x2, y2, z2, G)
         return dy, dgamma, dbeta, None, None, None, None, None, None, (da if has_res else None)
@@ -1309,7 +1310,7 @@ def bn_act_d2s(y, gamma, beta, running_mean, running_var, slope=0.0, momentum=0.
     return BnActD2sFn.apply(y, gamma, beta, running_mean, running_var, slope, momentum, eps, num_batches_tracked, residual)
 
 
-D2S_FUSE = int(__import__('os').environ.get('ARCO_D2S_FUSE', '1'))      # A/B switch: 0 = separate depth-to-space pass in UpsamplingDeconvBlock
+D2S_FUSE = _env_int('ARCO_D2S_FUSE', 1)      # A/B switch: 0 = separate depth-to-space pass in UpsamplingDeconvBlock
 
 
 class S2D3Fn(torch.autograd.Function):
@@ -1352,7 +1353,7 @@ class S2dSkipFn(torch.autograd.Function):
         return out
 
 
-S2D_SKIP = int(__import__('os').environ.get('ARCO_S2D_SKIP', '1'))      # A/B switch: 0 = inverse permutation + tensor-library add
+S2D_SKIP = _env_int('ARCO_S2D_SKIP', 1)      # A/B switch: 0 = inverse permutation + tensor-library add
 
 
 def s2d_skip(x):
@@ -1622,20 +1623,16 @@ def conv(x, weight, bias=None, residual=False, bias_grad_zero=False):
     return ConvFn.apply(x, weight, bias, residual, bias_grad_zero)
 
 
-_LAST_CAT_BUF = None
-
-
 def conv_bn_act(x, weight, bias, gamma, beta, running_mean, running_var, slope=0.01, p=0.0, drop_mode=1,
                 momentum=0.1, eps=1e-5, num_batches_tracked=None, cat_room=0, pool=False):
     """`num_batches_tracked` (int64 buffer) is incremented inside the BN finalize kernel.
     cat_room > 0: the result is written as the leading channels of a buffer with `cat_room` more channels
     (`result._arco_cat_buf`), so that `upcat` can append an upsampled tensor behind it without a copy.
     pool=True: returns (result, maxpool2(result)) from one apply pass (2-D, p == 0)."""
-    global _LAST_CAT_BUF
     y = ConvBnActFn.apply(x, weight, bias, gamma, beta, running_mean, running_var, slope, p, drop_mode,
                           momentum, eps, num_batches_tracked, cat_room, pool)
     if cat_room:
-        (y[0] if pool else y)._arco_cat_buf, _LAST_CAT_BUF = _LAST_CAT_BUF, None
+        _take_cat_buf(y, pool)
     return y
 
 
@@ -1871,10 +1868,7 @@ class GnActFn(torch.autograd.Function):
             ctx.affine = False
         else:
             ctx.affine = True
-        nblk = L.query("arco_chan_stats_blocks", m // nb)
-        ssum = torch.empty((co, nb * nblk), dtype=torch.float32, device=z.device)
-        ssq = torch.empty((co, nb * nblk), dtype=torch.float32, device=z.device)
-        L.call("arco_chan_stats", L.ptr(zr), ldz, m, co, L.ptr(ssum), L.ptr(ssq), nb)
+        ssum, ssq, nblk = _batch_stats(zr, ldz, m, co, nb)      # groups = samples
         mean = torch.empty(nb * co, dtype=torch.float32, device=z.device)      # [N][co]
         istd = torch.empty(nb * co, dtype=torch.float32, device=z.device)
         L.call("arco_gn_finalize", L.ptr(ssum), L.ptr(ssq), nb * nblk, co, int(cpg), nb, m // nb, float(eps), L.ptr(mean), L.ptr(istd))
