@@ -1029,6 +1029,10 @@ template <typename TS>
 static int gather_rows_impl(const TS* src, long ld_src, int D, const int32_t* list, const int64_t* idx64,
                             const int32_t* idx32, long first, long n, float* out, long ld_out, void* stream) {
   ARCO_CHECK_ARG(D > 0 && n >= 0);
+  // D % 4 == 0 takes four elements per access (ld4f + a 16-byte store): row strides and base pointers must keep them aligned
+  if ((D & 3) == 0)
+    ARCO_CHECK_ARG((ld_src & 3) == 0 && (ld_out & 3) == 0 && (reinterpret_cast<uintptr_t>(src) % (4 * sizeof(TS))) == 0 &&
+                   (reinterpret_cast<uintptr_t>(out) & 15) == 0);
   if (n == 0) return ARCO_OK;
   hipLaunchKernelGGL(gather_rows_kernel<TS>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), src, ld_src, D, list,
                      idx64, idx32, first, n, out, ld_out);

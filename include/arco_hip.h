@@ -44,7 +44,8 @@ int arco_lv_weights(const uint64_t* codes, long n_pix, int C, int Cp, float* W, 
 int arco_weighted_row_sum(const float* T, long ldt, const float* Wt, long ldw, long n_rows, int C, int D,
                           const int64_t* totals, float* partial, float* out, long ldo, void* stream);
 /* out[j] = src[list ? list[idx[j]] : idx[j]], idx = idx64 | idx32 | identity, j in [first, first+n)
- * (rep[mask][idx] / rep_teacher[negative_mask], loss_helper_3d.py:403,455-457).                           */
+ * (rep[mask][idx] / rep_teacher[negative_mask], loss_helper_3d.py:403,455-457).  D % 4 == 0: four elements per
+ * access - ld_src and ld_out multiples of 4, src aligned to four elements, out to 16 bytes (else ARCO_ERR_ARG). */
 int arco_gather_rows(const float* src, long ld_src, int D, const int32_t* list, const int64_t* idx64,
                      const int32_t* idx32, long first, long n, float* out, long ld_out, void* stream);
 /* the same two with an f16 row matrix as the source (BASELINE.json configs[4], --act_dtype f16: the V-Net's full-resolution
