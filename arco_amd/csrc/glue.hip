@@ -298,9 +298,13 @@ __global__ void unsup_loss_final_kernel(const double* __restrict__ part, int B, 
     double s[4] = {0, 0, 0, 0};
     for (int k = threadIdx.x; k < nblk; k += 64) for (int i = 0; i < 4; ++i) s[i] += part[((long)b * nblk + k) * 4 + i];
     for (int i = 0; i < 4; ++i) s[i] = wave_sum_d(s[i]);
-    const double w = s[0] / s[1];
+    // an image without a selected pixel (no valid label among them) adds nothing: masked_select(w, ce > 0) never picks one of its
+    // pixels, while w = n_conf / 0 is inf or NaN and inf * 0 would turn the loss of the whole batch into NaN
+    const bool any_sel = s[3] > 0.0;
+    const double w = any_sel ? s[0] / s[1] : 0.0;
     if (threadIdx.x == 0) stats[b] = w;
-    num += w * s[2]; cnt += s[3];
+    if (any_sel) num += w * s[2];
+    cnt += s[3];
   }
   if (threadIdx.x != 0) return;
   stats[B] = cnt;
@@ -597,6 +601,7 @@ int arco_softmax_rows(const float* X, long ld, long M, int C, long P, float* pro
 }
 
 int arco_label_onehot(const int64_t* lab, long M, int C, long P, int64_t* out, void* stream) {
+  ARCO_CHECK_ARG(lab && out && C >= 1 && M > 0 && P > 0);
   hipLaunchKernelGGL(onehot_kernel, dim3(gl_grid(M)), dim3(256), 0, as_stream(stream), lab, M, C, P, out);
   return arco_launch_status();
 }
@@ -646,6 +651,7 @@ int arco_eqv_loss_fwd(const float* P_, long ldp, const float* Q_, long ldq, cons
 }
 int arco_eqv_loss_bwd(const float* P_, long ldp, const float* Q_, long ldq, const float* mask, int B, long P, int C,
                       const double* ws, const float* g, float* dP, long ldo, void* stream) {
+  ARCO_CHECK_ARG(P_ && Q_ && mask && ws && g && dP && B > 0 && P > 0 && C >= 1);
   hipLaunchKernelGGL(eqv_loss_bwd_kernel, dim3(gl_grid((long)B * P)), dim3(256), 0, as_stream(stream), P_, ldp, Q_, ldq, mask, P,
                      (long)B * P, C, B, ws + (long)unsup_nblk(B) * 2 * B, g, dP, ldo);
   return arco_launch_status();
@@ -783,6 +789,7 @@ int arco_sup_loss_fwd(const float* X, long ld, long M, int C, const int64_t* lab
 }
 int arco_sup_loss_bwd(const float* X, long ld, long M, int C, const int64_t* lab, const double* ws, const float* g_ce,
                       const float* g_dice, float* dX, long ldo, void* stream) {
+  ARCO_CHECK_ARG(X && lab && ws && g_ce && g_dice && dX && C >= 1 && C <= GL_MAXC && M > 0);
   const double* sums = ws + 1024l * (2 + 3 * C);
   if (C <= 4) hipLaunchKernelGGL(sup_loss_bwd_kernel<4>, dim3(gl_grid(M)), dim3(256), 0, as_stream(stream), X, ld, M, C, lab, sums, g_ce, g_dice, dX, ldo);
   else if (C <= 8) hipLaunchKernelGGL(sup_loss_bwd_kernel<8>, dim3(gl_grid(M)), dim3(256), 0, as_stream(stream), X, ld, M, C, lab, sums, g_ce, g_dice, dX, ldo);
@@ -821,6 +828,7 @@ int arco_unsup_loss_fwd(const float* X, long ld, int B, long P, int C, const int
 }
 int arco_unsup_loss_bwd(const float* X, long ld, int B, long P, int C, const int64_t* lab, const double* ws, const float* g,
                         float* dX, long ldo, void* stream) {
+  ARCO_CHECK_ARG(X && lab && ws && g && dX && C >= 1 && C <= GL_MAXC && B > 0 && P > 0);
   hipLaunchKernelGGL(unsup_loss_bwd_kernel, dim3(gl_grid((long)B * P)), dim3(256), 0, as_stream(stream), X, ld, P, (long)B * P, C,
                      lab, ws + (long)unsup_nblk(B) * 4 * B, B, g, dX, ldo);
   return arco_launch_status();
