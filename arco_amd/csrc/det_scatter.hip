@@ -188,7 +188,7 @@ int arco_det_absmax(const float* X, long ld, int C, long n, unsigned* maxbits, v
 
 int arco_det_scatter_rows(const float* src, long ld_src, int C, int div, const int32_t* list, const int64_t* idx, const float* w,
                           long n_e, long long* acc, long ld_acc, const unsigned* maxbits, void* stream) {
-  ARCO_CHECK_ARG(src && idx && acc && maxbits && C > 0 && div >= 1 && (reinterpret_cast<uintptr_t>(acc) & 7) == 0);
+  ARCO_CHECK_ARG(src && idx && acc && maxbits && C > 0 && div >= 1 && n_e >= 0 && (reinterpret_cast<uintptr_t>(acc) & 7) == 0);
   if (n_e == 0) return ARCO_OK;
   hipLaunchKernelGGL(det_scatter_rows_kernel, dim3((unsigned)((n_e + 3) / 4)), dim3(256), 0, as_stream(stream), src, ld_src, C, div, list,
                      idx, w, n_e, acc, ld_acc, maxbits);
@@ -197,7 +197,7 @@ int arco_det_scatter_rows(const float* src, long ld_src, int C, int div, const i
 
 int arco_det_finish_rows(const int32_t* list, const int64_t* idx, long n_e, const long long* acc, long ld_acc, int C,
                          const unsigned* maxbits, float alpha, float* dst, long ld_dst, void* stream) {
-  ARCO_CHECK_ARG(idx && acc && maxbits && dst && C > 0);
+  ARCO_CHECK_ARG(idx && acc && maxbits && dst && C > 0 && n_e >= 0);
   if (n_e == 0) return ARCO_OK;
   hipLaunchKernelGGL(det_finish_rows_kernel, dim3((unsigned)((n_e + 3) / 4)), dim3(256), 0, as_stream(stream), list, idx, n_e, acc, ld_acc,
                      C, maxbits, alpha, dst, ld_dst);
@@ -205,7 +205,7 @@ int arco_det_finish_rows(const int32_t* list, const int64_t* idx, long n_e, cons
 }
 
 int arco_det_clear_rows(const int32_t* list, const int64_t* idx, long n_e, long long* acc, long ld_acc, int C, void* stream) {
-  ARCO_CHECK_ARG(idx && acc && C > 0);
+  ARCO_CHECK_ARG(idx && acc && C > 0 && n_e >= 0);
   if (n_e == 0) return ARCO_OK;
   hipLaunchKernelGGL(det_clear_rows_kernel, dim3((unsigned)((n_e + 3) / 4)), dim3(256), 0, as_stream(stream), list, idx, n_e, acc, ld_acc, C);
   return arco_launch_status();
@@ -213,7 +213,7 @@ int arco_det_clear_rows(const int32_t* list, const int64_t* idx, long n_e, long 
 
 int arco_corner_rows3d(const int64_t* pix, long n, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int64_t* idx8, float* w8,
                        void* stream) {
-  ARCO_CHECK_ARG(pix && idx8 && w8 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0);
+  ARCO_CHECK_ARG(pix && idx8 && w8 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0 && n >= 0);
   if (n == 0) return ARCO_OK;
   hipLaunchKernelGGL(corner_rows3d_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), pix, n, Di, Hi, Wi, Do, Ho, Wo,
                      idx8, w8);
@@ -221,21 +221,21 @@ int arco_corner_rows3d(const int64_t* pix, long n, int Di, int Hi, int Wi, int D
 }
 
 int arco_corner_rows2d(const int64_t* pix, long n, int Hi, int Wi, int Ho, int Wo, int64_t* idx4, float* w4, void* stream) {
-  ARCO_CHECK_ARG(pix && idx4 && w4 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0);
+  ARCO_CHECK_ARG(pix && idx4 && w4 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && n >= 0);
   if (n == 0) return ARCO_OK;
   hipLaunchKernelGGL(corner_rows2d_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), pix, n, Hi, Wi, Ho, Wo, idx4, w4);
   return arco_launch_status();
 }
 
 int arco_row_nonzero(const float* X, long ld, int C, long M, unsigned char* flag, void* stream) {
-  ARCO_CHECK_ARG(X && flag && C > 0 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0);
+  ARCO_CHECK_ARG(X && flag && C > 0 && M >= 0 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0);
   if (M == 0) return ARCO_OK;
   hipLaunchKernelGGL(row_nonzero_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, as_stream(stream), X, ld, C, M, flag);
   return arco_launch_status();
 }
 
 int arco_put_rows(const float* src, long ld_src, int C, const int64_t* idx, long n, float* dst, long ld_dst, void* stream) {
-  ARCO_CHECK_ARG(src && idx && dst && C > 0 && (ld_src & 3) == 0 && (ld_dst & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+  ARCO_CHECK_ARG(src && idx && dst && C > 0 && n >= 0 && (ld_src & 3) == 0 && (ld_dst & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(dst) & 15) == 0);
   if (n == 0) return ARCO_OK;
   hipLaunchKernelGGL(put_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, as_stream(stream), src, ld_src, C, idx, n, dst, ld_dst);

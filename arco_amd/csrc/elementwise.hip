@@ -1050,6 +1050,10 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ k, const f
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) k[i] = k[i] * m + q[i] * om;
 }
 
+// host-side pointer checks of the wrappers: 16-byte (f32x4) / 8-byte (four f16) vector accesses start at the base pointers
+static inline bool ew_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool ew_al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
 static inline int ew_grid(long work) {
   long g = (work + 255) / 256;
   if (g > 4096) g = 4096;
@@ -1403,14 +1407,18 @@ int arco_gather_upcat_rows_h(const float* lo, long ldlo, int Clo, int Hi, int Wi
 }
 int arco_scatter_upcat_rows(const float* dX, long ldx, const int64_t* pix, long n, float* dlo, long ldlo, int Clo, int Hi,
                             int Wi, float* dhi, long ldhi, int Chi, int Ho, int Wo, void* stream) {
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(dX && pix && (Clo == 0 || dlo) && (Chi == 0 || dhi));
   hipLaunchKernelGGL(scatter_upcat_rows_kernel, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), dX, ldx, pix, n, dlo,
                      ldlo, Clo, Hi, Wi, dhi, ldhi, Chi, Ho, Wo);
   return arco_launch_status();
 }
 
 int arco_up_neighbors(const int64_t* pix, long n, int Hi, int Wi, int Ho, int Wo, int64_t* nb4, float* lylx, void* stream) {
+  ARCO_CHECK_ARG(n >= 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && nb4 && lylx);
   hipLaunchKernelGGL(up_neighbors_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), pix, n, Hi, Wi, Ho, Wo, nb4, lylx);
   return arco_launch_status();
 }
@@ -1432,28 +1440,32 @@ int arco_lerp4_cat_rows_h(const float* V, long ldv, int Clo, const float* lylx, 
 }
 int arco_lerp4_cat_rows_bwd(const float* dX, long ldx, int Clo, const float* lylx, const int64_t* pix, long n, float* dV,
                             long ldv, float* dhi, long ldhi, int Chi, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (ldv & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && (Clo & 3) == 0 && (ldv & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(dX && lylx && pix && (Clo == 0 || (dV && ew_al16(dV))) && (Chi == 0 || dhi) && ew_al16(dX));
   hipLaunchKernelGGL(lerp4_cat_rows_bwd_kernel, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), dX, ldx, Clo, lylx, pix,
                      n, dV, ldv, dhi, ldhi, Chi);
   return arco_launch_status();
 }
 
 int arco_s2d3(float* V, long ldv, int NV, int X2, int Y2, int Z2, int C, float* P, long ldp, int dir, void* stream) {
-  ARCO_CHECK_ARG((C & 3) == 0 && (ldv & 3) == 0 && (ldp & 3) == 0);
+  ARCO_CHECK_ARG(V && P && NV > 0 && X2 > 0 && Y2 > 0 && Z2 > 0 && C > 0 && (dir == 0 || dir == 1) && (C & 3) == 0 && (ldv & 3) == 0 &&
+                 (ldp & 3) == 0 && ew_al16(V) && ew_al16(P));
   hipLaunchKernelGGL(s2d3_kernel, dim3(ew_grid((long)NV * X2 * Y2 * Z2 * 8 * (C / 4))), dim3(256), 0, as_stream(stream), V, ldv,
                      NV, X2, Y2, Z2, C, P, ldp, dir);
   return arco_launch_status();
 }
 // V[(n, 2x+dx, 2y+dy, 2z+dz)][c] = P[(n, x, y, z)][tap * C + c] + ADD[(same voxel)][c]   (tap = dx*4 + dy*2 + dz)
 int arco_d2s3_add(const float* P, long ldp, int NV, int X2, int Y2, int Z2, int C, const float* ADD, long lda, float* V, long ldv, void* stream) {
-  ARCO_CHECK_ARG(P && ADD && V && (C & 3) == 0 && (ldp & 3) == 0 && (lda & 3) == 0 && (ldv & 3) == 0);
+  ARCO_CHECK_ARG(P && ADD && V && NV > 0 && X2 > 0 && Y2 > 0 && Z2 > 0 && C > 0 && (C & 3) == 0 && (ldp & 3) == 0 && (lda & 3) == 0 &&
+                 (ldv & 3) == 0 && ew_al16(P) && ew_al16(ADD) && ew_al16(V));
   hipLaunchKernelGGL(d2s3_add_kernel<float>, dim3(ew_grid((long)NV * X2 * Y2 * Z2 * 8 * (C / 4))), dim3(256), 0, as_stream(stream), P, ldp,
                      NV, X2, Y2, Z2, C, ADD, lda, V, ldv);
   return arco_launch_status();
 }
 int arco_d2s3_add_h(const void* P, long ldp, int NV, int X2, int Y2, int Z2, int C, const void* ADD, long lda, void* V, long ldv, void* stream) {
-  ARCO_CHECK_ARG(P && ADD && V && (C & 3) == 0 && (ldp & 3) == 0 && (lda & 3) == 0 && (ldv & 3) == 0);
+  ARCO_CHECK_ARG(P && ADD && V && NV > 0 && X2 > 0 && Y2 > 0 && Z2 > 0 && C > 0 && (C & 3) == 0 && (ldp & 3) == 0 && (lda & 3) == 0 &&
+                 (ldv & 3) == 0 && ew_al8(P) && ew_al8(ADD) && ew_al8(V));
   hipLaunchKernelGGL(d2s3_add_kernel<_Float16>, dim3(ew_grid((long)NV * X2 * Y2 * Z2 * 8 * (C / 4))), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<const _Float16*>(P), ldp, NV, X2, Y2, Z2, C, reinterpret_cast<const _Float16*>(ADD), lda,
                      reinterpret_cast<_Float16*>(V), ldv);
@@ -1461,14 +1473,16 @@ int arco_d2s3_add_h(const void* P, long ldp, int NV, int X2, int Y2, int Z2, int
 }
 int arco_trilinear_fwd(const float* X, long ldx, int NV, int Di, int Hi, int Wi, int C, int Do, int Ho, int Wo, float* Y,
                        long ldy, void* stream) {
-  ARCO_CHECK_ARG((C & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0);
+  ARCO_CHECK_ARG(X && Y && NV > 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0 && C > 0 && (C & 3) == 0 && (ldx & 3) == 0 &&
+                 (ldy & 3) == 0 && ew_al16(X) && ew_al16(Y));
   hipLaunchKernelGGL(trilinear_fwd_kernel, dim3(ew_grid((long)NV * Do * Ho * Wo * (C / 4))), dim3(256), 0, as_stream(stream),
                      X, ldx, NV, Di, Hi, Wi, C, Do, Ho, Wo, Y, ldy);
   return arco_launch_status();
 }
 int arco_trilinear_bwd(const float* dY, long ldy, int NV, int Di, int Hi, int Wi, int C, int Do, int Ho, int Wo, float* dX,
                        long ldx, void* stream) {
-  ARCO_CHECK_ARG((C & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0);
+  ARCO_CHECK_ARG(dY && dX && NV > 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0 && C > 0 && (C & 3) == 0 && (ldx & 3) == 0 &&
+                 (ldy & 3) == 0 && ew_al16(dY) && ew_al16(dX));
   hipLaunchKernelGGL(trilinear_bwd_kernel, dim3(ew_grid((long)NV * Di * Hi * Wi * (C / 4))), dim3(256), 0, as_stream(stream),
                      dY, ldy, NV, Di, Hi, Wi, C, Do, Ho, Wo, dX, ldx);
   return arco_launch_status();
@@ -1476,8 +1490,10 @@ int arco_trilinear_bwd(const float* dY, long ldy, int NV, int Di, int Hi, int Wi
 
 int arco_gather_upcat_rows3d(const float* lo, long ldlo, int Clo, int Di, int Hi, int Wi, const float* hi, long ldhi, int Chi,
                              int Do, int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldlo & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0 && (Clo & 3) == 0 && (Chi & 3) == 0 &&
+                 (ldlo & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && X && (Clo == 0 || (lo && ew_al16(lo))) && (Chi == 0 || (hi && ew_al16(hi))) && ew_al16(X));
   hipLaunchKernelGGL(gather_upcat_rows3d_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), lo, ldlo, Clo, Di, Hi, Wi,
                      hi, ldhi, Chi, Do, Ho, Wo, pix, n, X, ldx);
   return arco_launch_status();
@@ -1485,8 +1501,10 @@ int arco_gather_upcat_rows3d(const float* lo, long ldlo, int Clo, int Di, int Hi
 // ... with the full-resolution map `hi` stored as f16 (f16 activation storage); lo, X fp32
 int arco_gather_upcat_rows3d_h(const float* lo, long ldlo, int Clo, int Di, int Hi, int Wi, const void* hi, long ldhi, int Chi,
                                int Do, int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldlo & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0 && (Clo & 3) == 0 && (Chi & 3) == 0 &&
+                 (ldlo & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && X && (Clo == 0 || (lo && ew_al16(lo))) && (Chi == 0 || (hi && ew_al8(hi))) && ew_al16(X));
   hipLaunchKernelGGL(gather_upcat_rows3d_kernel<_Float16>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), lo, ldlo, Clo, Di, Hi, Wi,
                      reinterpret_cast<const _Float16*>(hi), ldhi, Chi, Do, Ho, Wo, pix, n, X, ldx);
   return arco_launch_status();
@@ -1494,29 +1512,36 @@ int arco_gather_upcat_rows3d_h(const float* lo, long ldlo, int Clo, int Di, int 
 // rows of cat(trilinear blend of eight already-evaluated corner rows, hi[pix]) and the blend's adjoint (three-level 3-D head)
 int arco_lerp8_cat_rows3d(const float* V, long ldv, int Clo, int Di, int Hi, int Wi, const float* hi, long ldhi, int Chi,
                           int Do, int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0 && (Clo & 3) == 0 && (Chi & 3) == 0 &&
+                 (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && X && (Clo == 0 || (V && ew_al16(V))) && (Chi == 0 || (hi && ew_al16(hi))) && ew_al16(X));
   hipLaunchKernelGGL(lerp8_cat_rows3d_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), V, ldv, Clo, Di, Hi, Wi,
                      hi, ldhi, Chi, Do, Ho, Wo, pix, n, X, ldx);
   return arco_launch_status();
 }
 int arco_lerp8_cat_rows3d_h(const float* V, long ldv, int Clo, int Di, int Hi, int Wi, const void* hi, long ldhi, int Chi,
                             int Do, int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0 && (Clo & 3) == 0 && (Chi & 3) == 0 &&
+                 (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && X && (Clo == 0 || (V && ew_al16(V))) && (Chi == 0 || (hi && ew_al8(hi))) && ew_al16(X));
   hipLaunchKernelGGL(lerp8_cat_rows3d_kernel<_Float16>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), V, ldv, Clo, Di, Hi, Wi,
                      reinterpret_cast<const _Float16*>(hi), ldhi, Chi, Do, Ho, Wo, pix, n, X, ldx);
   return arco_launch_status();
 }
 int arco_lerp8_rows3d_bwd(const float* dX, long ldx, int Clo, const float* w8, long n, float* dV, long ldv, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (ldv & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && (Clo & 3) == 0 && (ldv & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(dX && w8 && dV && ew_al16(dX) && ew_al16(dV));
   hipLaunchKernelGGL(lerp8_rows3d_bwd_kernel, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), dX, ldx, Clo, w8, n, dV, ldv);
   return arco_launch_status();
 }
 int arco_scatter_upcat_rows3d(const float* dX, long ldx, const int64_t* pix, long n, float* dlo, long ldlo, int Clo, int Di,
                               int Hi, int Wi, float* dhi, long ldhi, int Chi, int Do, int Ho, int Wo, void* stream) {
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(dX && pix && (Clo == 0 || dlo) && (Chi == 0 || dhi));
   hipLaunchKernelGGL(scatter_upcat_rows3d_kernel, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), dX, ldx, pix, n, dlo,
                      ldlo, Clo, Di, Hi, Wi, dhi, ldhi, Chi, Do, Ho, Wo);
   return arco_launch_status();
@@ -1568,18 +1593,22 @@ int arco_combine_terms_bwd(const float* weights, int n, const float* g, float* g
 }
 
 int arco_copy_rows(const float* X, long ldx, long M, int C, float* Y, long ldy, int accumulate, void* stream) {
-  ARCO_CHECK_ARG((C & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0);
+  ARCO_CHECK_ARG(M >= 0 && C > 0 && (C & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0);
+  if (M == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(X && Y && ew_al16(X) && ew_al16(Y));
   hipLaunchKernelGGL(copy_rows_kernel, dim3(ew_grid(M * (C / 4))), dim3(256), 0, as_stream(stream), X, ldx, M, C, Y, ldy,
                      accumulate);
   return arco_launch_status();
 }
 
 int arco_nchw_to_nhwc(const float* X, int NB, int C, long P, float* Y, long ldy, void* stream) {
+  ARCO_CHECK_ARG(X && Y && P > 0 && C > 0 && NB >= 1 && NB <= 65535);      // (NB is the grid's z extent)
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((P + 31) / 32, (C + 31) / 32, NB), dim3(32, 8), 0, as_stream(stream), X,
                      NB, C, P, Y, ldy);
   return arco_launch_status();
 }
 int arco_nhwc_to_nchw(const float* X, long ldx, int NB, int C, long P, float* Y, void* stream) {
+  ARCO_CHECK_ARG(X && Y && P > 0 && C > 0 && NB >= 1 && NB <= 65535);
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3((P + 31) / 32, (C + 31) / 32, NB), dim3(32, 8), 0, as_stream(stream), X,
                      ldx, NB, C, P, Y);
   return arco_launch_status();
@@ -1587,6 +1616,9 @@ int arco_nhwc_to_nchw(const float* X, long ldx, int NB, int C, long P, float* Y,
 
 int arco_sgd_nesterov(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay,
                       int first, void* stream) {
+  ARCO_CHECK_ARG(n >= 0);
+  if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(p && g && buf);
   hipLaunchKernelGGL(sgd_nesterov_kernel, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), p, g, buf, n, lr, momentum,
                      weight_decay, first);
   return arco_launch_status();
@@ -1594,11 +1626,17 @@ int arco_sgd_nesterov(float* p, const float* g, float* buf, long n, float lr, fl
 // torch.optim.SGD(momentum, weight_decay, nesterov=False): the stage-1 trainers' optimizer (pretrain_2D.py:193-195)
 int arco_sgd_momentum(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay,
                       int first, void* stream) {
+  ARCO_CHECK_ARG(n >= 0);
+  if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(p && g && buf);
   hipLaunchKernelGGL(sgd_nesterov_kernel, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), p, g, buf, n, lr, momentum,
                      weight_decay, (first ? 1 : 0) | 2);
   return arco_launch_status();
 }
 int arco_ema(float* k, const float* q, long n, float m, void* stream) {
+  ARCO_CHECK_ARG(n >= 0);
+  if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(k && q);
   hipLaunchKernelGGL(ema_kernel, dim3(ew_grid(n)), dim3(256), 0, as_stream(stream), k, q, n, m);
   return arco_launch_status();
 }

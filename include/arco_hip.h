@@ -266,10 +266,15 @@ int arco_bilinear_bwd(const float* dY, long ldy, int NB, int Hi, int Wi, int C, 
  * FeatureExtractor.fea4 / q_representation: model_2D.py:51-53, train_arco_2d.py:324-325)                   */
 int arco_gather_upcat_rows(const float* lo, long ldlo, int Clo, int Hi, int Wi, const float* hi, long ldhi, int Chi,
                            int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream);
+/* (arco_scatter_upcat_rows: fp32 atomics, no alignment requirement; ARCO_ERR_ARG for n < 0, a negative channel count, a size <= 0 or,
+ * when n > 0, a null dX / pix / dlo (Clo > 0) / dhi (Chi > 0).  n == 0 returns ARCO_OK before any pointer is looked at, here and in
+ * every row kernel below.)                                                                                  */
 int arco_scatter_upcat_rows(const float* dX, long ldx, const int64_t* pix, long n, float* dlo, long ldlo, int Clo,
                             int Hi, int Wi, float* dhi, long ldhi, int Chi, int Ho, int Wo, void* stream);
 /* second level of the row-sparse head: explicit low-res neighbour rows of each anchor (ids + (ly,lx)),
  * their 4-way lerp + cat with the high-res map, and the adjoint                                            */
+/* (arco_up_neighbors rejects n < 0, a size <= 0 and null pointers; arco_lerp4_cat_rows_bwd also dX / dV that are not 16-byte
+ * aligned - it moves four channels at a time -, dV may be null only with Clo == 0, dhi only with Chi == 0) */
 int arco_up_neighbors(const int64_t* pix, long n, int Hi, int Wi, int Ho, int Wo, int64_t* nb4, float* lylx, void* stream);
 int arco_lerp4_cat_rows(const float* V, long ldv, int Clo, const float* lylx, const float* hi, long ldhi, int Chi,
                         const int64_t* pix, long n, float* X, long ldx, void* stream);
@@ -283,13 +288,19 @@ int arco_gather_upcat_rows_h(const float* lo, long ldlo, int Clo, int Hi, int Wi
 int arco_lerp4_cat_rows_h(const float* V, long ldv, int Clo, const float* lylx, const void* hi, long ldhi, int Chi,
                           const int64_t* pix, long n, float* X, long ldx, void* stream);
 /* V-Net k2s2 (transposed) convs as GEMMs over packed 2x2x2 blocks (vnetWithArgs.py:67-118); trilinear
- * align_corners resize of FeatureExtractor_3d (model_3D.py:46-58)                                          */
+ * align_corners resize of FeatureExtractor_3d (model_3D.py:46-58).
+ * All three move four channels (16 bytes) per access: C and the strides are multiples of 4, the base pointers 16-byte aligned, every
+ * size positive, dir 0 or 1 - anything else is ARCO_ERR_ARG before a launch.                                */
 int arco_s2d3(float* V, long ldv, int NV, int X2, int Y2, int Z2, int C, float* P, long ldp, int dir, void* stream);
 int arco_trilinear_fwd(const float* X, long ldx, int NV, int Di, int Hi, int Wi, int C, int Do, int Ho, int Wo, float* Y,
                        long ldy, void* stream);
 int arco_trilinear_bwd(const float* dY, long ldy, int NV, int Di, int Hi, int Wi, int C, int Do, int Ho, int Wo, float* dX,
                        long ldx, void* stream);
-/* 3-D row-sparse head: rows of cat(trilinear_up(lo), hi) at selected voxels + adjoint (model_3D.py:52-55) */
+/* 3-D row-sparse head: rows of cat(trilinear_up(lo), hi) at selected voxels + adjoint (model_3D.py:52-55).
+ * The gathers (and arco_lerp8_cat_rows3d / arco_lerp8_rows3d_bwd below) move four channels per access: channel counts and strides are
+ * multiples of 4, lo / V / X / dX / dV 16-byte aligned, hi 16-byte (f16: 8-byte) aligned; sizes positive, n >= 0, channel counts >= 0;
+ * lo may be null only with Clo == 0, hi only with Chi == 0 (an operand of no channels is never read: neither its pointer nor its
+ * alignment is looked at).  The scatter uses scalar fp32 atomics: the null and size checks only.                                  */
 int arco_gather_upcat_rows3d(const float* lo, long ldlo, int Clo, int Di, int Hi, int Wi, const float* hi, long ldhi, int Chi,
                              int Do, int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream);
 int arco_scatter_upcat_rows3d(const float* dX, long ldx, const int64_t* pix, long n, float* dlo, long ldlo, int Clo, int Di,
@@ -316,7 +327,13 @@ int arco_zero_rows_h(void* dst, long ld, int C, const int64_t* idx, long n, void
  *   arco_det_scatter_rows:  acc[r(e)][c] += fix(w[e] * src[e / div][c]),  r(e) = list ? list[idx[e]] : idx[e],  e < n_e  (w nullable = 1)
  *   arco_det_finish_rows:   dst[r(e)][c]  = alpha * fp32(acc[r(e)][c])    (nan when the source was non-finite)
  *   arco_det_clear_rows:    acc[r(e)][c]  = 0                             (acc: persistent, zero between uses)
- *   arco_corner_rows3d:     idx8[8j+k], w8[8j+k] = low-resolution row and weight of corner k of sampled voxel pix[j]            */
+ *   arco_corner_rows3d:     idx8[8j+k], w8[8j+k] = low-resolution row and weight of corner k of sampled voxel pix[j]
+ * An all-zero source (maxbits[0] == 0): arco_det_scatter_rows adds nothing and arco_det_finish_rows WRITES NOTHING - dst keeps what it
+ * held, so a caller that needs zeros there fills them itself (arco_amd/head.py does).  A non-finite source: nothing is accumulated
+ * and finish writes the quiet NaN 0x7fc00000 into every named row.
+ * Arguments: n / n_e / M < 0, C <= 0, div < 1 and a null pointer (list and w excepted) are ARCO_ERR_ARG before any launch; acc is
+ * 8-byte aligned.  n_e == 0 (arco_corner_rows*: n == 0) is a no-op that returns ARCO_OK; arco_det_absmax with n == 0 still sets
+ * maxbits[0] = 0.                                                                                                                  */
 int arco_det_absmax(const float* X, long ld, int C, long n, unsigned* maxbits, void* stream);
 int arco_det_scatter_rows(const float* src, long ld_src, int C, int div, const int32_t* list, const int64_t* idx, const float* w,
                           long n_e, long long* acc, long ld_acc, const unsigned* maxbits, void* stream);
@@ -331,7 +348,8 @@ int arco_corner_rows2d(const int64_t* pix, long n, int Hi, int Wi, int Ho, int W
  * model_2D.py:51-53, train_arco_2d.py:231-234, 324-326).  The loss reads `rep` at a few hundred sampled rows (loss_helper_3d.py:455-457),
  * so d loss / d rep - and, the layers being per-pixel, every gradient down to the first resampling - is zero in all other rows:
  *   arco_row_nonzero: flag[r] = any element of row r that is not +-0   (one pass over the gradient)
- *   arco_put_rows:    dst[idx[j]] = src[j]  (idx unique: the compacted data gradient back into a zero tensor)                          */
+ *   arco_put_rows:    dst[idx[j]] = src[j]  (idx unique: the compacted data gradient back into a zero tensor)
+ * Both read four channels at a time: strides multiples of 4, X / src / dst 16-byte aligned; M / n < 0 is ARCO_ERR_ARG, 0 a no-op.       */
 int arco_row_nonzero(const float* X, long ld, int C, long M, unsigned char* flag, void* stream);
 int arco_put_rows(const float* src, long ld_src, int C, const int64_t* idx, long n, float* dst, long ld_dst, void* stream);
 /* glue kernels replacing chains of tensor-library launches in the step (no reference counterpart: the reference's
@@ -344,12 +362,15 @@ int arco_fold_residual(const float* W, int n, int c, float* lo, float* hi, void*
 int arco_unfold_residual(const float* dlo, const float* dhi, int n, int c, float* dW, void* stream);
 int arco_combine_terms(const float* const* terms, const float* weights, int n, float* out, void* stream);
 int arco_combine_terms_bwd(const float* weights, int n, const float* g, float* grads, void* stream);
+/* arco_copy_rows: C and the strides multiples of 4, X / Y non-null and 16-byte aligned, M >= 0 (0: nothing to do), C > 0.
+ * The layout transposes: non-null pointers, P > 0, C > 0, NB in 1 .. 65535 (the grid's z extent).                        */
 int arco_copy_rows(const float* X, long ldx, long M, int C, float* Y, long ldy, int accumulate, void* stream);
 int arco_nchw_to_nhwc(const float* X, int NB, int C, long P, float* Y, long ldy, void* stream);
 int arco_nhwc_to_nchw(const float* X, long ldx, int NB, int C, long P, float* Y, void* stream);
 
 /* ---- O1/N5  torch.optim.SGD(nesterov) step and EMA over flat buffers (train_arco_2d.py:248,306-308,431-432;
  *      model_2D.py:176-182)                                                                                */
+/* (n < 0 and, for n > 0, null pointers are ARCO_ERR_ARG; n == 0 does nothing - arco_sgd_momentum and arco_ema alike) */
 int arco_sgd_nesterov(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay,
                       int first, void* stream);
 /* the same with nesterov=False (stage-1 pre-training: pretrain_2D.py:193-195, pretrain_3D.py) */
@@ -500,6 +521,7 @@ int arco_bn_act_d2s_bwd_h(const void* dA, long ldd, const void* Y, long M8, int 
                           void* dY, int X2, int Y2, int Z2, int groups, void* stream);
 /* V = depth_to_space(P) + ADD: the gradient of an encoder activation that feeds both the next DownsamplingConvBlock (through
  * space-to-depth) and the decoder's skip connection (vnetWithArgs.py:186-201,224-236), one pass instead of arco_s2d3 + an add    */
+/* (non-null pointers, 16-byte aligned - f16: 8-byte -, positive sizes, C and the strides multiples of 4) */
 int arco_d2s3_add(const float* P, long ldp, int NV, int X2, int Y2, int Z2, int C, const float* ADD, long lda, float* V, long ldv, void* stream);
 int arco_d2s3_add_h(const void* P, long ldp, int NV, int X2, int Y2, int Z2, int C, const void* ADD, long lda, void* V, long ldv, void* stream);
 int arco_cast_h2f(const void* x, long n, float* y, void* stream);
