@@ -160,6 +160,7 @@ _QUERIES = {   # plain host helpers returning sizes
     "arco_conv_mblocks_pro": ([_I, _I, _I, _I, _I, _I, _L, _I, _I, _I], _I),
     "arco_conv_config": ([_I, _I, _I, _I, _I, _I, _L, _P], _I),
     "arco_conv_config_mma": ([_I, _I, _I, _I, _I, _I, _L, _I], _I),
+    "arco_conv_last_route": ([], _I),
     "arco_conv_split_ok": ([_I, _I, _I, _I, _I, _I, _L], _I),
     "arco_conv_pro_ok": ([_I, _I, _I, _I, _I, _I, _I, _L, _I, _I], _I),
     "arco_conv_sp_set": ([_I], _I),

@@ -350,6 +350,7 @@ static int launch_fl(const IgemmArgs& a, hipStream_t st, int* q) {
   const int mblocks = a.NB * ((a.H * (a.W + 2) + G::BM - 1) / G::BM);
   if (q) { q[0] = 4 * mblocks; q[1] = 9270000 + A_T * 1000 + G::BN; q[2] = 1630; return ARCO_OK; }      // 4 stat slabs per tile
   if (a.D3 < 1 || a.NB % a.D3 != 0) return ARCO_ERR_ARG;
+  arco_note_route(9270000 + A_T * 1000 + G::BN);
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = a.Npad / G::BN;
   const int total = mblocks * b.n_nblocks, cus = conv_sp_cus();
@@ -767,6 +768,7 @@ static int launch_fc(const IgemmArgs& a, hipStream_t st, int* q) {
   if (a.D3 < 1 || a.NB % a.D3 != 0) return ARCO_ERR_ARG;
   const size_t lds = G::lds_bytes(a.W + 2, fc_pro_dw(a));
   if (lds > 160 * 1024) return ARCO_ERR_UNSUPPORTED;
+  arco_note_route(9290000 + (A_T + (NCW == 8 ? 5 : 0)) * 1000 + G::BN);
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = a.Npad / G::BN;
   const int total = mblocks * b.n_nblocks, cus = conv_sp_cus();
@@ -1139,6 +1141,7 @@ static int launch_dw(const IgemmArgs& a, hipStream_t st, int* q) {
   const int mblocks = a.NB * per_plane;
   if (q) { q[0] = 4 * mblocks; q[1] = 9280000 + A_T * 1000 + G::BN; q[2] = 1630; return ARCO_OK; }
   if (a.D3 < 1 || a.NB % a.D3 != 0) return ARCO_ERR_ARG;
+  arco_note_route(9280000 + A_T * 1000 + G::BN);
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = a.Npad / G::BN;
   // column height: the columns should about fill the CUs once (one workgroup per CU); never below 2 planes (each column stages two

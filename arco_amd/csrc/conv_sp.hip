@@ -748,6 +748,7 @@ static int launch_rw(const IgemmArgs& a, hipStream_t st, int* q) {
   const int mblocks = a.NB * (a.H / G::TH) * (a.W / 16);
   if (q) { q[0] = NCW * mblocks; q[1] = 9350000 + (G::TH / 4) * 1000 + G::BN; q[2] = 1610; return ARCO_OK; }      // (id by tile height: <4,1,NCW=8> is <8,1>'s tile)
   if ((a.ldc & 3) != 0 || (a.R && (a.ldr & 3) != 0)) return ARCO_ERR_UNSUPPORTED;
+  arco_note_route(9350000 + (G::TH / 4) * 1000 + G::BN);
   const size_t lds = G::lds_bytes((a.K + 15) >> 4);
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = 1;
@@ -773,6 +774,7 @@ static int launch_sp(const IgemmArgs& a, hipStream_t st, int* q) {
   const int mblocks = a.NB * (a.H / G::TH) * (a.W / 16);
   if (q) { q[0] = 4 * mblocks; q[1] = 9300000 + A_T * 1000 + G::BN; q[2] = 1610; return ARCO_OK; }      // 4 stat slabs per tile
   if ((a.ldc & 3) != 0 || (a.R && (a.ldr & 3) != 0)) return ARCO_ERR_UNSUPPORTED;
+  arco_note_route(9300000 + A_T * 1000 + G::BN);
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = a.Npad / G::BN;
   const int total = mblocks * b.n_nblocks, cus = conv_sp_cus();
@@ -969,6 +971,7 @@ int conv3d_rw_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
   if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_rw16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES); }
   IgemmArgs b = a;
   b.n_mblocks = (int)(a.NB * tiles);
+  arco_note_route(9 * 1000000 + 450000 + 16);
   hipLaunchKernelGGL(conv3d_rw16_kernel, dim3((unsigned)(slots < units ? slots : units)), dim3(G::NT), G::LDS_BYTES, st, b, S, nseg);
   return arco_launch_status();
 }

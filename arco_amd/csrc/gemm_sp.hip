@@ -426,6 +426,7 @@ int gemm_sp_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = nblocks;
   const int grid = (int)(tiles < n_cu ? tiles : n_cu);
+  arco_note_route(1000000 + BM * 1000 + BN + (a.Rup ? 450000 : 400000));      // gemm_sp_kernel<false> 1464256, <true> (fused upsample) 1514256
   if (a.Rup) hipLaunchKernelGGL(gemm_sp_kernel<true>, dim3(grid), dim3(512), 2 * BUF_DW * 4, st, b);
   else hipLaunchKernelGGL(gemm_sp_kernel<false>, dim3(grid), dim3(512), 2 * BUF_DW * 4, st, b);
   return arco_launch_status();

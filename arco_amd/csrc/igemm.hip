@@ -476,6 +476,7 @@ static int launch_igemm_v(const IgemmArgs& a, hipStream_t st, int* n_mblocks_out
     n_mblocks_out[2] = KC * 100 + DEPTH * 10 + (DB ? 1 : 0);
     return ARCO_OK;
   }
+  arco_note_route(TAPS * 1000000 + BM * 1000 + BN + (FLAT ? 500000 : 0));
   constexpr int LDKL = MMA == 3 ? (KC / 16) * 24 + (KC == 32 ? 8 : 0) : KC + 4;
   size_t sh = (size_t)(DB ? 2 : 1) * (AROWS + TAPS * BN + (MMA == 3 ? 1 : 0)) * LDKL * sizeof(float);
   const size_t red = (size_t)2 * WAVES_M * BN * sizeof(float);
@@ -723,6 +724,7 @@ static int launch_halo(const IgemmArgs& a, hipStream_t st, int* q) {
   if (bpg < 1) bpg = 1;
   const long blocks = bpg * n_grp;
   if (q) { q[0] = (int)blocks; q[1] = 9 * 1000000 + 900000 + CIN * 1000 + COUT; q[2] = CIN * 100 + 10; return ARCO_OK; }
+  arco_note_route(9 * 1000000 + 900000 + CIN * 1000 + COUT);
   auto kern = conv3x3_halo_kernel<CIN, COUT, TW>;
   static unsigned long long attr_set = 0;
   if (sh > 64 * 1024 && arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); }
@@ -896,6 +898,7 @@ static int launch_image_conv3d(const IgemmArgs& a, hipStream_t st, int* q) {
   if (q) { q[0] = (int)blocks; q[1] = 9 * DEPTH * 1000000 + 700000 + 1000 + 16; q[2] = 10; return ARCO_OK; }
   IgemmArgs b = a; b.n_mblocks = (int)blocks; b.n_nblocks = 1;
   if (DEPTH == 1) b.D3 = 1;
+  arco_note_route(9 * DEPTH * 1000000 + 700000 + 1000 + 16);
   hipLaunchKernelGGL(conv3d_image_kernel<DEPTH>, dim3((unsigned)blocks), dim3(256), 0, st, b);
   return arco_launch_status();
 }
@@ -910,6 +913,7 @@ static int launch_image_conv(const IgemmArgs& a, hipStream_t st, int* q) {
   const long blocks = bpg * n_grp;
   if (q) { q[0] = (int)blocks; q[1] = 9 * 1000000 + 800000 + a.K * 1000 + 16; q[2] = 10; return ARCO_OK; }
   IgemmArgs b = a; b.n_mblocks = (int)blocks; b.n_nblocks = 1;
+  arco_note_route(9 * 1000000 + 800000 + a.K * 1000 + 16);
   hipLaunchKernelGGL(conv3x3_image_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b);
   return arco_launch_status();
 }
@@ -994,6 +998,7 @@ static int conv1x1_stream_dispatch(const IgemmArgs& a, hipStream_t st) {
     const int Q = a.K / 4;
     long blocks = (a.M + (256 / Q) * rows_per_block_min - 1) / ((256 / Q) * rows_per_block_min);
     if (blocks > 16384) blocks = 16384;
+    arco_note_route(1600000 + a.K * 1000 + 4);      // (launch-only routes: ids beside the others in include/arco_hip.h)
     switch (Q) {
       case 1: hipLaunchKernelGGL(conv1x1_narrow_out_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
       case 2: hipLaunchKernelGGL(conv1x1_narrow_out_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, st, a); break;
@@ -1008,6 +1013,7 @@ static int conv1x1_stream_dispatch(const IgemmArgs& a, hipStream_t st) {
     const int Q = a.N / 4;
     long blocks = (a.M + (256 / Q) * rows_per_block_min - 1) / ((256 / Q) * rows_per_block_min);
     if (blocks > 16384) blocks = 16384;
+    arco_note_route(1700000);
     hipLaunchKernelGGL(conv1x1_narrow_in_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
     return arco_launch_status();
   }
@@ -2027,7 +2033,15 @@ __global__ void transpose2d_kernel(const float* __restrict__ x, long ldx, int ro
   }
 }
 
+thread_local int arco_last_route = 0;
+
 extern "C" {
+
+// Test-facing: the id (as arco_conv_config_mma reports it) of the kernel that the most recent forward launch of this thread took.  Every
+// forward entry point sets it to 0 once its arguments have passed, so it is 0 before the first launch, after a call that found no
+// kernel (ARCO_ERR_UNSUPPORTED) and after a launch through conv_h.hip (mma 4), whose kernels do not note theirs; a call rejected
+// with ARCO_ERR_ARG leaves it unchanged.
+int arco_conv_last_route(void) { return arco_last_route; }
 
 // Query: number of M-blocks (= BN-stat partial slabs per channel) the conv launch will use.
 int arco_conv_mblocks(int taps, int NB, int H, int W, int Cin, int Cout, long ld_in, int stat_groups) {
@@ -2151,6 +2165,7 @@ int arco_pack_many(const void* desc, int n_desc, long total, void* stream) {
 int arco_gemm_splitk(const float* in, long ld_in, int K, const float* Wp, int N, float* out, long ld_out, long M,
                      int splits, float* ws, void* stream) {
   ARCO_CHECK_ARG(in && Wp && out && ws && K > 0 && N > 0 && M > 0 && splits >= 1 && (ld_out & 3) == 0);
+  arco_note_route(0);
   IgemmArgs a{};
   a.A = in; a.lda = ld_in; a.Wp = Wp; a.N = N; a.K = K;
   a.Npad = (N + 15) / 16 * 16; a.Kpad = (K + 15) / 16 * 16;
@@ -2181,6 +2196,7 @@ int arco_gemm_batched(const float* in, long ld_in, int K, const float* Wp, int N
                       int batch, long stride_in, long stride_w, long stride_out, int splits, float* ws, void* stream) {
   ARCO_CHECK_ARG(in && Wp && out && K > 0 && N > 0 && M > 0 && batch >= 1 && splits >= 1 && (ld_out & 3) == 0);
   ARCO_CHECK_ARG(splits == 1 || (ws && (stride_out & 3) == 0));
+  arco_note_route(0);
   IgemmArgs a{};
   a.A = in; a.lda = ld_in; a.Wp = Wp; a.N = N; a.K = K;
   a.Npad = (N + 15) / 16 * 16; a.Kpad = (K + 15) / 16 * 16;
@@ -2211,6 +2227,7 @@ int arco_conv_fwd(const float* in, long ld_in, int K, const float* Wp, int N, fl
 int arco_conv1x1_upres_fwd(const float* in, long ld_in, int K, const float* Wp, int N, float* out, long ld_out, const float* lo,
                            long ld_lo, int NV, int uD, int uH, int uW, int oD, int oH, int oW, void* stream) {
   ARCO_CHECK_ARG(in && Wp && out && lo && K > 0 && N > 0 && NV > 0 && uD > 0 && uH > 0 && uW > 0 && oD > 0 && oH > 0 && oW > 0);
+  arco_note_route(0);
   IgemmArgs a{};
   a.A = in; a.lda = ld_in; a.Wp = Wp; a.N = N; a.K = K;
   a.Npad = (N + 15) / 16 * 16;
@@ -2287,6 +2304,7 @@ static int conv3d_fwd_impl(const float* in, long ld_in, int K, const float* Wp, 
     a.Kpad = taps == 1 ? a.Kg * 16 : (K + 15) / 16 * 16;
   }
   ARCO_CHECK_ARG(NV % a.stat_groups == 0);
+  arco_note_route(0);
   if (pro && taps == 27) {      // (arco_conv_pro_ok has vouched for the shape: conv3d_fc_kernel<.., PRO>)
     a.pro = *pro;
     const int r = conv3d_fl_dispatch(a, as_stream(stream), nullptr);

@@ -195,6 +195,11 @@ __device__ __forceinline__ s16x4 to_bf16x4(f32x4 v) {
   return r;
 }
 
+// arco_conv_last_route (include/arco_hip.h, test-facing): every launch_* / *_dispatch function notes the id of the kernel it launches -
+// the id its query form reports in q[1] - in this per-thread word.  Host side only: one thread-local store per launch.
+extern thread_local int arco_last_route;
+static inline void arco_note_route(int id) { arco_last_route = id; }
+
 // conv_sp.hip: the software-pipelined split-bf16 3x3 kernel.  Returns -1 when the shape is not one it takes (the caller
 // then falls through to igemm_kernel), otherwise the launch status; q != nullptr: query only (q[0] = M-tiles = BN stat
 // slabs per channel, q[1] = instantiation id, q[2] = KC*100 + DEPTH*10).

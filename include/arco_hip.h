@@ -141,9 +141,21 @@ int arco_conv_mblocks(int taps, int NB, int H, int W, int Cin, int Cout, long ld
 int arco_conv_mblocks_mma(int taps, int NB, int H, int W, int Cin, int Cout, long ld_in, int stat_groups, int mma);   /* ... for a launch in matrix-core mode mma (arco_conv3d_fwd) */
 int arco_conv_mblocks_pro(int taps, int NB, int H, int W, int Cin, int Cout, long ld_in, int stat_groups, int mma, int pro_groups);   /* ... for a launch through arco_conv3d_fwd_pro (3x3x3: the forms with the activation in their loaders tile differently) */
 /* which kernel instantiation a launch uses: igemm_kernel<TAPS,BM,BN,..> -> TAPS*1e6 + BM*1e3 + BN;
- * conv3x3_halo_kernel<CIN,COUT,..> -> 9.9e6 + CIN*1e3 + COUT */
+ * conv3x3_halo_kernel<CIN,COUT,..> -> 9.9e6 + CIN*1e3 + COUT; conv3x3_image_kernel -> 9.8e6 + CIN*1e3 + 16; conv3d_image_kernel<DEPTH> ->
+ * 9*DEPTH*1e6 + 701016; conv3d_rw16_kernel -> 9450016; the flat 3x3x3 igemm tiles add 5e5; conv_sp.hip / conv3d_fl.hip: see below.
+ * Launch-only routes, which no query describes and only arco_conv_last_route reports:
+ *   conv1x1_narrow_out_kernel<Q> -> 1.6e6 + K*1e3 + 4 (K = 4 Q = 4, 8, 16, 32: 1604004, 1608004, 1616004, 1632004)
+ *   conv1x1_narrow_in_kernel     -> 1700000
+ *   gemm_sp_kernel<false>        -> 1464256 (1e6 + 4e5 + BM*1e3 + BN, 64 x 256 tiles);  gemm_sp_kernel<true> (fused upsample) -> 1514256 */
 int arco_conv_config(int taps, int NB, int H, int W, int Cin, int Cout, long ld_in, int* kc_depth_db);
 int arco_conv_config_mma(int taps, int NB, int H, int W, int Cin, int Cout, long ld_in, int mma);
+/* test-facing: the id, as above, of the kernel that the most recent forward launch on the calling thread took (arco_conv_fwd,
+ * arco_conv3d_fwd(_pro), arco_gemm_splitk, arco_gemm_batched, arco_conv1x1_upres_fwd).  Each of these sets it to 0 once its arguments
+ * have passed: it is 0 before the first launch, after a call that found no kernel (ARCO_ERR_UNSUPPORTED, such as a refused
+ * arco_conv1x1_upres_fwd) and after a launch on the kernels of conv_h.hip (mma 4), which do not note theirs - the one-channel 3x3x3
+ * volume runs on conv3d_image_kernel<3> in mma 4 too and reports 27701016.  A call rejected with ARCO_ERR_ARG leaves it unchanged.
+ * Host side only: nothing on the device changes. */
+int arco_conv_last_route(void);
 /* A/B switch of the software-pipelined split-bf16 3x3 kernel (conv_sp.hip; ids 9.3e6 + A_T*1e3 + BN, resident-weights form 9.35e6 + ...): on = 1 (default,
  * or ARCO_CONV_SP=0 in the environment for off) lets the eligible wide 2-D shapes take it, 0 keeps every shape on
  * igemm_kernel.  Returns the previous setting.  Tile counts differ: query arco_conv_mblocks_mma after switching.   */

@@ -15,6 +15,8 @@ def test_library_exports_header_symbols():
     for name in declared:
         assert hasattr(lib, name), name
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
+    assert "arco_conv_last_route" in declared          # the test-facing record of the kernel a forward launch took
+    assert isinstance(_lib.query("arco_conv_last_route"), int)
 
 
 def test_missing_library_fails_loudly(monkeypatch):
