@@ -19,6 +19,21 @@ from . import glue, graphs, ops, optim
 from .loss_scale import LossScaleGuard
 
 
+def schedule_levels(value):
+    """(train_arco_2d.TEACHER_SIDE, train_arco_3d.PASS_SIDE) for ARCO_TEACHER_SIDE = `value` (None: unset).  The step has two
+    schedules: the concurrent one (unset or "4": independent passes side by side on a second stream) and the single-stream one
+    ("0": the reference of the parity tests, bench.py's per-kernel timing).  The levels in between are retired: no run under an
+    old label on another schedule."""
+    if value is None or value == "4":
+        return 4, 3
+    if value == "0":
+        return 0, 0
+    raise ValueError(f"ARCO_TEACHER_SIDE={value}: the step has two schedules, 4 (or unset: concurrent) and 0 (single-stream)")
+
+
+SCHEDULE = schedule_levels(os.environ.get("ARCO_TEACHER_SIDE"))      # the one read of the variable, for both trainers
+
+
 class ArcoStepBase(LossScaleGuard):
     def _set_modes(self, conv_mma, act_half, head_mma, wgrad_side):
         """THE place that writes the process-wide switches of arco_amd.ops, all five together: called once by each constructor, after

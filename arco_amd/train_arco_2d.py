@@ -156,26 +156,26 @@ def patients_to_slices(dataset, patiens_num):
     return ref_dict[str(patiens_num)]
 
 
-# Pass-level concurrency on a second stream (round 4; profiles/r04_notes.md section 7).  The step is a dependent chain of ~870 kernels,
-# most of them 5-40 us: a kernel rarely fills the chip for its whole duration, and one launch floor (~5 us) per link adds up to a
-# third of the step.  Running two INDEPENDENT passes side by side fills those gaps - unlike kernel-level forks inside one pass
-# (ops._wgrad), which made the persistent kernels of the same pass fight for CUs.
-#   1: the teacher's grouped pass beside the student forward                                  13.30 -> 13.16 ms
-#   2: + the statistics-only student pass (cj2_l) beside the masks / heads work               -> 12.87 ms
-#   3: + the warped student pass (equivariance term) on the side stream: its forward beside the heads / InfoNCE, its BACKWARD
-#      beside the main pass's backward, parameter gradients into a second flat buffer          -> 11.37 ms
-#   4: + the step's critical path shortened (tools/step_timeline.py): the statistics pass moves to the step's start, beside the
-#      teacher's first pass (its running-statistics updates postponed into slot 1 of ops.bn_defer, so they still land between l
-#      and u); warps + warped pass start on the side stream as soon as the host has drawn the warp, the bank appends are
-#      queued after them                                                  same process, alternating: 11.64 -> 11.27 ms  (default)
-# Results are unchanged: the passes were independent already, only their order in time is free; the two gradient buffers are
-# summed once (a + b, bit-identical to accumulating in sequence).  ARCO_TEACHER_SIDE=0 restores the single-stream step.
-TEACHER_SIDE = int(os.environ.get("ARCO_TEACHER_SIDE", "4"))
+# The step's two schedules.  The step is a dependent chain of ~870 kernels, most of them 5-40 us: a kernel rarely fills the chip for its
+# whole duration, and one launch floor (~5 us) per link adds up to a third of the step.  Running two INDEPENDENT passes side by side
+# fills those gaps.  TEACHER_SIDE is read every time the step runs, and only its truth matters there:
+#   4 (default), the concurrent schedule.  On the side stream `_t_stream`: the statistics-only student pass (cj2_l) from the step's
+#     start, beside the teacher's first pass (its running-statistics updates postponed into slot 1 of ops.bn_defer, so they still land
+#     between l and u; joined before the grouped passes); the teacher's grouped pass beside the student's (joined behind it); the
+#     warps and the warped student pass of the equivariance term (when the pass replays its captured graph, --graph_train 1; an
+#     eager one stays in line) from the moment the host has drawn the warp - forward beside the
+#     heads / InfoNCE (joined before its loss), backward beside the main pass's backward, parameter gradients into a second flat
+#     buffer (joined and summed once after backward(): a + b, bit-identical to accumulating in sequence); the bank appends are queued
+#     after that pass.  On a third stream `_img_stream`, with cutout / cutmix: the image side of the mixing strategy and of the two
+#     batch_transform calls beside the teacher's first pass (joined behind it).
+#   0, the single-stream schedule (ARCO_TEACHER_SIDE=0): every pass in line.  bench.py times kernels under it; the parity tests hold
+#     the concurrent schedule to it - the passes were independent already, only their order in time is free.
+# Measurements, and the schedules in between that lost theirs: profiles/r04_notes.md section 7 to profiles/r06_notes.md.
+TEACHER_SIDE = stepper.SCHEDULE[0]
 # SIDE_SYNC (round 4's host-side wait in front of loss.backward()) is OFF since round 5: the non-reproducible gradient it hid was a
 # gfx950 erratum in ONE compiler-generated instruction of arco_lerp4_cat_rows_bwd, fixed in the kernel (csrc/elementwise.hip,
 # tests/test_isa_lint.py, profiles/r05_notes.md section 1).  ARCO_SIDE_SYNC=1 restores the wait (A/B only).
 SIDE_SYNC = int(os.environ.get("ARCO_SIDE_SYNC", "0"))
-IMG_EARLY = int(os.environ.get("ARCO_IMG_EARLY", "1"))     # see ArcoStep2D.step (with TEACHER_SIDE >= 4)
 
 
 class ArcoStep2D(ArcoStepBase):
@@ -238,11 +238,12 @@ class ArcoStep2D(ArcoStepBase):
         self.profile_loss = False
         self.loss_events = []
         self._t_stream = self._img_stream = None     # side streams, created on first use (self._stream)
-        self._stats_on_side = self._tps_on_side = False
+        self._tps_on_side = False
         use_graphs, g_train = self._build_graphs()
-        # the equivariance term's student pass (:415).  ARCO_TEACHER_SIDE >= 3: replayed on the side stream - its forward beside the
-        # heads / InfoNCE, its backward beside the main pass's backward - with a gradient buffer of its own (optim.second_grad_views)
-        self._tps_side = TEACHER_SIDE >= 3 and g_train
+        # the equivariance term's student pass (:415).  Concurrent schedule: replayed on the side stream - its forward beside the
+        # heads / InfoNCE, its backward beside the main pass's backward - with a gradient buffer of its own (optim.second_grad_views).
+        # Fixed here: the captured graph writes into that buffer whatever TEACHER_SIDE says when the step runs
+        self._tps_side = bool(TEACHER_SIDE) and g_train
         self.s_train_tps = graphs.GraphedTrain(self.model, enabled=g_train,
                                                grad_views=self.optimizer.second_grad_views() if self._tps_side else None)
         self.s_fwd_stats = graphs.GraphedForward(self.model, enabled=use_graphs)
@@ -298,22 +299,22 @@ class ArcoStep2D(ArcoStepBase):
             augment.draw_batch_transform_params(int(l_data.shape[0]), False)         # (only its generator draws matter)
             cj2_l, _, _ = augment.batch_transform(l_data, l_label, torch.ones_like(l_label, dtype=torch.float32), a.patch_size,
                                                   (1.0, 1.0), False)
-        stats_early = TEACHER_SIDE >= 4 and self.batched_passes and l_data.shape == u_data.shape
+        stats_early = bool(TEACHER_SIDE and self.batched_passes and l_data.shape == u_data.shape)      # concurrent and batched
         if stats_early:
-            # Mode 4: the statistics-only student pass on images_cj2_l (:311) depends on nothing but the weights - it runs on the
+            # The statistics-only student pass on images_cj2_l (:311) depends on nothing but the weights - it runs on the
             # side stream beside the teacher's first pass (two 8-image passes, neither of which fills the chip alone).  Its
             # running-statistics updates are postponed (slot 1) and land between those of the l and the u half of the grouped
             # student pass below: the reference's order l, cj2_l, u.
             self._stream("_t_stream").wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self._t_stream), torch.no_grad(), ops.bn_defer(0, 1), self._fm_none():
                 self.s_fwd_stats(cj2_l)
-        # IMG_EARLY (cutout / cutmix): the IMAGE side of the mixing strategy and of the two batch_transform calls (:296-304) reads no
+        # img_early (concurrent and batched, cutout / cutmix): the IMAGE side of the mixing strategy and of the two batch_transform calls (:296-304) reads no
         # pseudo-label - the boxes, ColorJitter / blur parameters and AdvMorph fields are host / generator draws, labels pass through
         # batch_transform unchanged and the confidences are only quantised (augment.batch_transform) - so it is queued on a third stream
         # NOW, beside the teacher's first pass and the statistics pass, instead of alone between them and the grouped passes (0.4 ms of
         # small launches).  Same host draws in the same order (the teacher's pass draws nothing); labels and confidences are mixed with
         # the same boxes once the pseudo-labels exist.
-        img_early = bool(IMG_EARLY and stats_early and a.apply_aug in ("cutout", "cutmix"))
+        img_early = stats_early and a.apply_aug in ("cutout", "cutmix")
         if img_early:
             mix_desc = augment.draw_boxes(int(u_data.shape[0]), tuple(int(v) for v in u_data.shape[2:]))
             self._stream("_img_stream").wait_stream(torch.cuda.current_stream())
@@ -356,7 +357,7 @@ class ArcoStep2D(ArcoStepBase):
             # The u half postpones its running-statistics update (ops.bn_defer) until the images_cj2_l pass below has
             # made its own: the momentum updates then land in the reference's order l, cj2_l, u (:310-312).
             t_side = None
-            if TEACHER_SIDE:      # the teacher's grouped pass (independent of the student's) on a second stream, beside the student forward
+            if TEACHER_SIDE:      # concurrent: the teacher's grouped pass (independent of the student's) on a second stream, beside the student forward
                 t_side = self._stream("_t_stream")
                 t_side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(t_side), torch.no_grad(), ops.bn_groups(2), self._fm_t():
@@ -409,12 +410,6 @@ class ArcoStep2D(ArcoStepBase):
             if stats_early:
                 ops.apply_deferred_bn(1)                                 # cj2_l (ran beside the teacher's first pass), then
                 ops.apply_deferred_bn()                                  # the u half / pass
-            elif TEACHER_SIDE >= 2 and batched:    # (mode 2: this statistics-only pass too runs beside the main stream's work)
-                self._stream("_t_stream").wait_stream(torch.cuda.current_stream())     # behind the student pass: BN buffers in the reference's order
-                with torch.cuda.stream(self._t_stream), self._fm_none():
-                    self.s_fwd_stats(cj2_l)
-                    ops.apply_deferred_bn()
-                self._stats_on_side = True
             else:
                 with self._fm_none():
                     self.s_fwd_stats(cj2_l)
@@ -437,7 +432,7 @@ class ArcoStep2D(ArcoStepBase):
         # k4*loss_q (revisiting loss; no gradient path to any parameter) only with --revisit 1.
         loss_ce, loss_dice = glue.supervised_loss(pred_l, l_label)
         unsup_loss = glue.compute_unsupervised_loss(pred_u, u_aug_label, u_aug_logits, a.strong_threshold)
-        eqv_in = None
+        eqv_in, tps_on_side = None, False
         if a.k2 != 0:
             # inputs of the equivariance term that depend neither on the counters nor on the warp: queued BEFORE the host
             # blocks on the counters (the stretch between the counters' arrival and the warped student pass is the part
@@ -448,7 +443,13 @@ class ArcoStep2D(ArcoStepBase):
                 logits_all = torch.cat((u_aug_logits.new_ones(l_label.shape), u_aug_logits))
                 eqv_in = (glue.eqv_mask(labels_all, logits_all, a.weak_threshold), torch.cat((cj2_l, cj2_u)),
                           pred_all.detach() if batched else torch.cat((pred_l.detach(), pred_u.detach())))
-            if TEACHER_SIDE >= 4:          # mode 4: the warps and the warped pass start from here on the side stream
+            # Where the warped pass runs is decided by how the stepper was BUILT: its captured graph writes its parameter gradients
+            # into the second buffer, so a replay belongs on the side stream and has to set optimizer._g2_dirty even when a stepper
+            # built under the concurrent schedule is stepped with TEACHER_SIDE = 0 (bench.py and the tests turn the graph off
+            # before they do that, so neither reaches this corner; without it that gradient would never be merged).
+            with self._fm_none():          # (the mode the warped pass is captured under: GraphedTrain replays under no other)
+                tps_on_side = self._tps_side and self.s_train_tps.will_replay(eqv_in[1])
+            if tps_on_side:                # the warps and the warped pass start from here on the side stream
                 self._eqv_in_ready = torch.cuda.Event()
                 self._eqv_in_ready.record()
         # per-class row lists and prototypes need the class codes / totals on the DEVICE only: queued before the host blocks
@@ -471,11 +472,10 @@ class ArcoStep2D(ArcoStepBase):
                                 lazy_teacher=lazy_t, defer_anchor_pix=True)
             if prof:
                 ev2[1].record()
-        enqueue_late = TEACHER_SIDE >= 4 and a.k2 != 0    # mode 4: the warped pass is on the step's critical path - queue it first
-        if not enqueue_late:
+        warp_first = bool(TEACHER_SIDE and a.k2 != 0)     # concurrent: the warped pass is on the step's critical path - queue it first
+        if not warp_first:
             enqueue()
         C_.contrast_draw(plan, a.func, defer=True)     # indices collected by contrast_anchor_pix below
-        tps_on_side = tps_early = False
         loss_eqv = None
         if a.k2 != 0:
             # equivariance term (:404-423).  The warp is drawn AFTER the samplers, as in the reference: both consume
@@ -484,45 +484,25 @@ class ArcoStep2D(ArcoStepBase):
             if self.tps is None or self.tps.batch_size != nb2:
                 self.tps = self._make_tps(nb2, l_data.device)            # :255-261 (draws one warp, like the reference)
             eq_mask, images_cj2, pred_all_d = eqv_in
-            with self._fm_none():          # (the mode the warped pass is captured under: GraphedTrain replays under no other)
-                tps_on_side = self._tps_side and self.s_train_tps.will_replay(images_cj2)
-            tps_early = tps_on_side and TEACHER_SIDE >= 4
             if tps_on_side:
-                self._stream("_t_stream")
-            if tps_early:
-                # Mode 4: the warps and the warped pass do not queue behind the main stream's row lists / bank appends / index
-                # uploads: they run on the side stream from the moment the host has drawn the warp, behind `eqv_in` on the main
-                # stream (which is behind the grouped pass and the running-statistics updates above).
-                self._t_stream.wait_event(self._eqv_in_ready)
-            with torch.cuda.stream(self._t_stream) if tps_early else contextlib.nullcontext():
+                # The warps and the warped pass do not queue behind the main stream's row lists / bank appends / index uploads:
+                # they run on the side stream from the moment the host has drawn the warp, behind `eqv_in` on the main stream
+                # (which is behind the grouped pass and the running-statistics updates above).
+                self._stream("_t_stream").wait_event(self._eqv_in_ready)
+            with torch.cuda.stream(self._t_stream) if tps_on_side else contextlib.nullcontext():
                 with torch.no_grad():
                     self.tps.reset_control_points()                      # :412
                     images_tps = self.tps(images_cj2)                    # :411-413 images_cj2
                     mask_tps = self.tps(eq_mask, padding_mode='zeros')
                     pred_tps_org = self.tps(pred_all_d, padding_mode='zeros')
-                if tps_early:
-                    with self._fm_none():                                # (reads the logits only)
-                        pred_tps = self.s_train_tps(images_tps)[0]       # :415
-            if tps_early:
-                self.optimizer._g2_dirty = True
-            elif tps_on_side:      # behind the statistics-only pass on that stream (running statistics: cj2_l, u, then this pass)
-                self._t_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(self._t_stream), self._fm_none():
-                    pred_tps = self.s_train_tps(images_tps)[0]
-                self._stats_on_side = False
+                with self._fm_none():                                    # (reads the logits only)
+                    pred_tps = self.s_train_tps(images_tps)[0]           # :415 one more student pass (one BN batch)
+            if tps_on_side:
                 self.optimizer._g2_dirty = True
             else:
-                if self._stats_on_side:    # the warped pass updates the same running statistics next
-                    torch.cuda.current_stream().wait_stream(self._t_stream)
-                    self._stats_on_side = False
-                with self._fm_none():
-                    pred_tps = self.s_train_tps(images_tps)[0]           # :415 one more student pass (one BN batch)
                 loss_eqv = glue.eqv_loss(pred_tps, pred_tps_org, mask_tps)   # :419-423
-        if enqueue_late:
+        if warp_first:
             enqueue()
-        if self._stats_on_side:            # (no equivariance pass: the optimiser must not change the weights under the statistics pass)
-            torch.cuda.current_stream().wait_stream(self._t_stream)
-            self._stats_on_side = False
         if prof:
             ev3[0].record()
         C_.contrast_anchor_pix(plan)

@@ -23,26 +23,22 @@ from .tps.rand_tps_3d import RandTPS as RandTPS3D
 from .model_3D import ISD_3d, FeatureExtractor_3d
 from .train_arco_2d import build_parser as _build_parser_2d
 
-# pass-level concurrency on a second stream (see train_arco_2d.TEACHER_SIDE): 1 = the teacher's grouped pass beside the student
-# forward, 2 = + the gradient-free warped student pass beside the heads / InfoNCE / backward.  ARCO_TEACHER_SIDE=0: off.
-# 3 (default; tools/step_timeline3d.py) = + the teacher's FeatureExtractor on the side stream behind its pass (beside the masks and the
-# student's FeatureExtractor), and the warped pass no longer queued behind the main stream's heads / row lists / loss forwards: it
-# starts as soon as the host has drawn the warp - beside that low-occupancy stretch instead of beside the backward pass.
-PASS_SIDE = min(3, int(os.environ.get("ARCO_TEACHER_SIDE", "4")))
-LISTS_SIDE = int(os.environ.get("ARCO_LISTS_SIDE", "1"))
+# The step's two schedules (see train_arco_2d.TEACHER_SIDE; same variable, ARCO_TEACHER_SIDE).  PASS_SIDE is read every time the step
+# runs, and only its truth matters there:
+#   3 (default), the concurrent schedule.  On the second stream `_side`: the teacher - with cutout / cutmix (the mixed images need the
+#     host-drawn boxes only) its first pass and its grouped pass as ONE pass over cat(u, l, u_aug) with three BatchNorm groups (running
+#     statistics updated group after group: u, l, u_aug - the reference's order, train_arco_3d.py:260-262, 286-287), with classmix (its
+#     masks are the pseudo-labels') the grouped pass alone, behind the first pass in line - beside the student's grouped pass (joined
+#     behind it); behind the teacher's pass its FeatureExtractor, then the row lists / prototypes, beside the masks and the student's
+#     FeatureExtractor (joined before the loss forwards); after iteration 0 the gradient-free warped pass, from the moment the host has
+#     drawn the warp (separate passes / ragged batch: behind everything queued so far), bank appends queued after it, joined before the
+#     optimiser changes the weights.
+#   0, the single-stream schedule (ARCO_TEACHER_SIDE=0): every pass in line; the reference of the parity tests, bench.py's kernel timing.
+# Measurements, and the schedules in between that lost theirs: profiles/r04_notes.md to profiles/r06_notes.md (section 20).
+PASS_SIDE = stepper.SCHEDULE[1]
 # lazy levels of the row-sparse heads: 2 = fea3 / fea4 on rows over the dense 56x56x40 map of fea2 (rounds 2-5), 3 = fea2 on rows too - the
 # 224-channel map at 56x56x40 (450 MB at the LA size) is never written (head.LazyHead3dFn with three maps, round 6)
 HEAD_LEVELS = int(os.environ.get("ARCO_HEAD3D_LEVELS", "3"))
-# ARCO_U0_SIDE=1: the teacher's first pass beside the grouped student pass (cutout / cutmix; see ArcoStep3D.step).  Opt-in: measured level
-# (LA 21.2-21.3 -> 21.3-21.4 ms, LiTS-f16 13.7 -> 13.6-13.7) - the teacher's two passes stay serial on the second stream, which is then the
-# longer one; running them beside each other as well needs their BatchNorm running-statistics updates deferred (profiles/r06_notes.md section 20)
-U0_SIDE = int(os.environ.get("ARCO_U0_SIDE", "0"))
-# T_MERGE (default; ARCO_T_MERGE=0: the serial order of rounds 2-5): the teacher's first pass and its grouped pass as ONE pass over
-# cat(u, l, u_aug) with three BatchNorm groups (running statistics updated group after group: u, l, u_aug - the reference's order,
-# train_arco_3d.py:260-262, 286-287), on the second stream beside the student's grouped pass.  Possible with cutout / cutmix, whose mixed
-# images need the host-drawn boxes only (classmix masks are the pseudo-labels': serial order).  LA 21.1-21.2 -> 20.3 ms, LiTS-f16 13.5-13.6 -> 13.2
-# on the same box (profiles/r06_notes.md section 20)
-T_MERGE = int(os.environ.get("ARCO_T_MERGE", "1"))
 FM_ROWS_HALF = int(os.environ.get("ARCO_FM_ROWS_HALF", "1"))     # --act_dtype f16: heads read the full-resolution maps as f16 (ops.fm_rows_half)
 FEA_DIM_3D = [128, 64, 32, 16, 16]
 REP_DIM_3D = 16                                  # train_arco_3d.py:148,207
@@ -103,7 +99,7 @@ class ArcoStep3D(ArcoStepBase):
         self.tps = self._make_tps(2 * args.batch_size, device) if getattr(args, "eqv_pass", 1) else None    # :231-237
         self._side, self._tps_pending = None, False      # side stream, created on first use (self._stream)
         use_graphs, _ = self._build_graphs()
-        self.t_fwd_ulu = graphs.GraphedForward(self.ema_model, enabled=use_graphs)      # T_MERGE: (u, l, u_aug) as one three-group pass
+        self.t_fwd_ulu = graphs.GraphedForward(self.ema_model, enabled=use_graphs)      # (u, l, u_aug) as one three-group pass
         # the warped student pass carries no gradient after iteration 0 (:390-393): replayed as one graph - its ~300 eager
         # launches sat right behind the sampler stage, the stretch of the step where the GPU waits for the host
         self.s_fwd_tps = graphs.GraphedForward(self.model, enabled=use_graphs)
@@ -126,24 +122,15 @@ class ArcoStep3D(ArcoStepBase):
         # f16 row-sparse gradients) - no dense cast of a full-resolution map in either direction (ops.fm_rows_half)
         rows_half = ops.ACT_HALF and FM_ROWS_HALF and not getattr(a, "dense_head", 0) and self.random_pool is None
         fm_ctx = ops.fm_rows_half if rows_half else contextlib.nullcontext
-        # (opt-in, U0_SIDE) The teacher's first pass (pseudo-labels, :260-262) runs ALONE at the head of the step (2.2 of 20.8 ms at the LA size).
+        # The teacher's first pass (pseudo-labels, :260-262) would run ALONE at the head of the step (2.2 of 20.8 ms at the LA size).
         # With cutout / cutmix the mixed IMAGES need only the boxes - host draws -, not the pseudo-labels: the boxes are drawn at the
         # reference's point of the generator order, the images are mixed at once, the grouped student pass starts on this stream while
-        # the teacher's first pass and, behind it on the same (second) stream, its grouped pass run beside it; labels and logits are
-        # mixed with the same boxes once the teacher is done.  classmix (its masks are the pseudo-labels') keeps the serial order.
-        u0_side = ((U0_SIDE or T_MERGE) and PASS_SIDE >= 1 and a.apply_aug in ("cutout", "cutmix") and self.batched_passes
-                   and l_data.shape == u_data.shape)
-        t_merge = bool(u0_side and T_MERGE)
+        # the teacher's first pass, merged into its grouped pass, runs beside it on the second; labels and logits are mixed with the
+        # same boxes once the teacher is done.  classmix (its masks are the pseudo-labels') keeps the serial order.
+        t_merge = bool(PASS_SIDE and a.apply_aug in ("cutout", "cutmix") and self.batched_passes and l_data.shape == u_data.shape)
         if t_merge:
             self._stream("_side")
             mix_desc = augment.draw_boxes(int(u_data.shape[0]), tuple(int(v) for v in u_data.shape[2:]))
-            u_aug = augment.mix_images(u_data, a.apply_aug, mix_desc)
-        elif u0_side:
-            mix_desc = augment.draw_boxes(int(u_data.shape[0]), tuple(int(v) for v in u_data.shape[2:]))
-            self._stream("_side").wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._side), torch.no_grad(), ops.logits_only():      # :260-262
-                pred_u0, _, _ = self.t_fwd_u0(u_data)
-                pseudo_logits, pseudo_labels = glue.softmax_max(pred_u0)
             u_aug = augment.mix_images(u_data, a.apply_aug, mix_desc)
         else:
             with torch.no_grad(), ops.logits_only():                         # :260-262
@@ -160,7 +147,7 @@ class ArcoStep3D(ArcoStepBase):
             lu = torch.cat((l_data, u_aug))
             nb_l = int(l_data.shape[0])
             t_side = None
-            if PASS_SIDE >= 1:      # the teacher's grouped pass on a second stream, beside the student forward (see train_arco_2d.TEACHER_SIDE)
+            if PASS_SIDE:      # concurrent: the teacher's grouped pass on a second stream, beside the student forward (see train_arco_2d.TEACHER_SIDE)
                 t_side = self._stream("_side")
                 t_side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(t_side), torch.no_grad():
@@ -174,26 +161,26 @@ class ArcoStep3D(ArcoStepBase):
                         with ops.bn_groups(2), fm_ctx():
                             pred_t, _, fm_t = self.t_fwd_lu(lu)              # :286-287
                     t_done = t_side.record_event()
-                    if PASS_SIDE >= 3 and not getattr(a, "dense_head", 0):   # :292-293 (the teacher's heads: joined before the row lists)
+                    if not getattr(a, "dense_head", 0):   # :292-293 (the teacher's heads: joined before the row lists)
                         kfe = self.k_feature_extractor
                         lazy_t_side = self._lazy_teacher(kfe, fm_t)
             with ops.bn_groups(2), fm_ctx():
                 pred_all, _, fm_s = self.s_train_lu(lu)                  # :283-284
             if t_side is not None:
                 torch.cuda.current_stream().wait_event(t_done)
-            if u0_side:          # (t_done lies behind the teacher's first pass on the same stream)
+            if t_merge:          # (t_done lies behind the teacher's merged pass)
                 if self.keep_debug:
                     dbg_pseudo = (pseudo_labels.clone(), pseudo_logits.clone())
                 _, u_aug_label, u_aug_logits = augment.generate_unsup_data_3d(u_data, pseudo_labels, pseudo_logits, mode=a.apply_aug, desc=mix_desc)
             pred_l, pred_u = ops.split_batch(pred_all, nb_l)
-            if PASS_SIDE >= 3:     # the warped pass's inputs (volumes, mixed labels, the grouped pass's logits) exist from here on
+            if PASS_SIDE:     # the warped pass's inputs (volumes, mixed labels, the grouped pass's logits) exist from here on
                 self._fwd_ready = torch.cuda.current_stream().record_event()
         else:
             with ops.bn_defer(0), fm_ctx():                              # running statistics: l first (:283), then u
                 pred_u, _, u_fm = self.s_train_u(u_aug)                  # :284
         with torch.no_grad():
             if batched:
-                if PASS_SIDE < 1:
+                if not PASS_SIDE:
                     with ops.bn_groups(2), fm_ctx():
                         pred_t, _, fm_t = self.t_fwd_lu(lu)              # :286-287
                 pred_l_t, pred_u_t = pred_t[:nb_l], pred_t[nb_l:]
@@ -210,7 +197,7 @@ class ArcoStep3D(ArcoStepBase):
         plan = C_.contrast_masks(label_l, label_u, prob_l_t, prob_u_t, low_mask_all, high_mask_all,
                                  delta_n=a.strong_threshold_u2pl)
         lists_done = None
-        if lazy_t_side is not None and LISTS_SIDE:
+        if lazy_t_side is not None:
             # row lists and prototypes need the masks and the TEACHER's heads only: on the side stream (behind those heads), beside
             # the student's FeatureExtractor on this one, instead of in line behind it
             self._side.wait_event(torch.cuda.current_stream().record_event())
@@ -242,9 +229,7 @@ class ArcoStep3D(ArcoStepBase):
             s_low = _lowres(qfe, fm_s)
         if lists_done is not None:
             torch.cuda.current_stream().wait_event(lists_done)
-        else:
-            if lazy_t_side is not None:
-                torch.cuda.current_stream().wait_stream(self._side)      # the teacher's FeatureExtractor (side stream)
+        else:       # (dense heads, separate passes, single-stream: in line)
             C_.contrast_lists_protos(plan, rep_all_teacher, lazy_t)     # row lists, prototypes: device-side inputs only
         # the loss forwards need neither counters nor samples: queued before the host blocks (see train_arco_2d.py)
         loss_ce, loss_dice = glue.supervised_loss(pred_l, l_label)       # :306-310
@@ -252,12 +237,14 @@ class ArcoStep3D(ArcoStepBase):
         # counters -> [sample-independent GPU work] -> sampler replay on the host -> anchors (see train_arco_2d.py)
         C_.contrast_counts(plan, self.memobank, self.queue_size,
                            adist.anchors_for_rank(a.num_queries, getattr(a, "anchors_per_rank", "split")), a.num_negatives)
-        tps_early = (PASS_SIDE >= 3 and batched and getattr(a, "eqv_pass", 1) and self.iter_num > 0 and self.s_fwd_tps.enabled)
+        # concurrent, after iteration 0: the gradient-free warped pass (a graph) runs on the second stream; batched: queued first
+        warp_side = bool(PASS_SIDE and getattr(a, "eqv_pass", 1) and self.iter_num > 0 and self.s_fwd_tps.enabled)
+        warp_first = bool(warp_side and batched)
 
         def enqueue():                     # teacher key rows -> banks (no generator draws, no use of the sampled indices)
             C_.contrast_enqueue(plan, rep_all_teacher, self.memobank, self.queue_ptrlis, self.queue_size, lazy_teacher=lazy_t,
                                 defer_anchor_pix=True)
-        if not tps_early:
+        if not warp_first:
             enqueue()
         C_.contrast_draw(plan, a.func, defer=True)     # indices collected by contrast_anchor_pix below
         loss_eqv = None
@@ -274,10 +261,9 @@ class ArcoStep3D(ArcoStepBase):
                     self.tps.reset_control_points()                      # :377
                     return (self.tps(torch.cat((l_data, u_aug))), self.tps(eq_mask, padding_mode='zeros'),
                             self.tps(torch.cat((pred_l.detach(), pred_u.detach())), padding_mode='zeros'))
-            side_ok = PASS_SIDE >= 2 and self.iter_num > 0 and self.s_fwd_tps.enabled
-            if side_ok:
+            if warp_side:
                 self._stream("_side")
-            if tps_early:
+            if warp_first:
                 # after iteration 0 the warped pass is a logged value and a running-statistics update (:390-393): nothing of this
                 # step waits for it.  Warps, pass and loss run on the second stream from the moment the host has drawn the warp -
                 # beside the heads' forwards, row lists and loss forwards of the main stream (a stretch of small launches), the
@@ -292,7 +278,7 @@ class ArcoStep3D(ArcoStepBase):
                 enqueue()
             else:
                 images_tps, mask_tps, pred_tps_org = warp_inputs()
-                if side_ok:    # (PASS_SIDE 2: behind everything queued on the main stream so far, beside InfoNCE and backward)
+                if warp_side:    # (concurrent and not batched: behind everything queued on the main stream so far, beside InfoNCE and backward)
                     self._side.wait_stream(torch.cuda.current_stream())
                     with torch.cuda.stream(self._side), torch.no_grad(), ops.logits_only():
                         pred_tps = self.s_fwd_tps(images_tps)[0]

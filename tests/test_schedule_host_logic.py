@@ -1,6 +1,8 @@
 """Host-side bookkeeping of the step schedule (no GPU work): the BatchNorm running-statistics deferral slots of ops.bn_defer
-(train_arco_2d mode 4 postpones the statistics pass's updates into slot 1 and the u half's into slot 0, so that they land in the
-reference's order l, cj2_l, u - train_arco_2d.py:310-312) and the workspace sizing of the per-image losses."""
+(train_arco_2d's concurrent schedule postpones the statistics pass's updates into slot 1 and the u half's into slot 0, so that they land in the
+reference's order l, cj2_l, u - train_arco_2d.py:310-312), which schedule ARCO_TEACHER_SIDE selects, and the workspace sizing of
+the per-image losses."""
+import pytest
 import torch
 
 from arco_amd import _lib as L, ops
@@ -31,6 +33,17 @@ def test_bn_defer_slots_are_separate_and_nest():
     for slot in (0, 1):
         ops._DEFERRED[slot].pop(key)
         ops._DEFER_TABLE.pop(slot, None)
+
+
+def test_schedule_levels_knows_two_schedules():
+    """stepper.schedule_levels: (train_arco_2d.TEACHER_SIDE, train_arco_3d.PASS_SIDE) from the value of ARCO_TEACHER_SIDE - the concurrent
+    schedule (unset or 4) or the single-stream one (0); a retired level is refused, not run under its old label."""
+    from arco_amd import stepper
+    assert stepper.schedule_levels(None) == (4, 3) and stepper.schedule_levels("4") == (4, 3)
+    assert stepper.schedule_levels("0") == (0, 0)
+    for retired in ("1", "2", "3", "x"):
+        with pytest.raises(ValueError, match="4.*0"):
+            stepper.schedule_levels(retired)
 
 
 def test_loss_slab_counts():

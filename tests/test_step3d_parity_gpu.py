@@ -216,11 +216,16 @@ def test_three_steps_3d_vs_cpu_oracle(variant):
     print(f"worst parameter-update deviation so far: L2 {_STATS['e2']:.3f} (bound 0.1), element-wise {_STATS['emax']:.3f} (bound 0.3)")
 
 
-@pytest.mark.parametrize("side_mode", [2, 3])
-def test_pass_concurrency_3d_equals_the_single_stream_step(side_mode):
-    """(side_mode 3: the teacher's FeatureExtractor behind its pass on the second stream, the warped pass started as soon as the host
-    has drawn the warp instead of behind the main stream's queue, bank appends queued after it.)  The 3-D step with the teacher's grouped pass and the gradient-free warped pass on the second stream (train_arco_3d.PASS_SIDE = 2,
-    the default) against the single-stream step (0), four steps from equal state: loss terms, weights, BatchNorm buffers."""
+@pytest.mark.parametrize("variant", ["default", "separate_passes", "classmix"])
+def test_pass_concurrency_3d_equals_the_single_stream_step(variant):
+    """The 3-D concurrent schedule (train_arco_3d.PASS_SIDE = 3, the default) against the single-stream step (0), four steps from equal
+    state: loss terms, weights, BatchNorm buffers.  `default` (cutmix): the teacher's two passes merged into one on the second stream
+    beside the student's grouped pass, its FeatureExtractor and the row lists behind it there, the gradient-free warped pass started
+    as soon as the host has drawn the warp instead of behind the main stream's queue, bank appends queued after it.
+    `separate_passes` (batched_passes off on both steppers): every pass of the two nets in line, the warped pass on the second stream
+    behind everything queued so far.  `classmix`: the teacher's grouped pass alone on the second stream, behind its first pass in line."""
+    side_mode = 3
+    extra = ["--apply_aug", "classmix"] if variant == "classmix" else []
     from arco_amd import ops, train_arco_3d as T3
     prev = T3.PASS_SIDE
     try:
@@ -229,9 +234,11 @@ def test_pass_concurrency_3d_equals_the_single_stream_step(side_mode):
             T3.PASS_SIDE = mode
             random.seed(3); np.random.seed(3); torch.manual_seed(3)
             args = T3.build_parser().parse_args(["--batch_size", "1", "--queue_size", "200", "--synthetic", "1", "--num_classes", "4",
-                                                 "--num_queries", "48", "--num_negatives", "16", "--k1", "1.0"])
+                                                 "--num_queries", "48", "--num_negatives", "16", "--k1", "1.0"] + extra)
             args.patch_size = [32, 32, 32]
             st = T3.ArcoStep3D(args, "cuda:0")
+            if variant == "separate_passes":
+                st.batched_passes = False
             for m in (st.model, st.ema_model):
                 _drop_off(m)
             sts.append(st)

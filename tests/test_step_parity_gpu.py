@@ -208,12 +208,12 @@ def test_cityscapes_shaped_step_runs():
     assert len(st.memobank) == 19 and all(b[0].shape[1] == 496 for b in st.memobank)
 
 
-def _trainer(graphs, seed_state):
+def _trainer(graphs, seed_state, extra=()):
     from arco_amd import train_arco_2d as T
     b, patch, C = 2, (64, 64), 4
     unet_sd, fe_sd, qrep_w = seed_state
     argv = ["--batch_size", str(b), "--queue_size", "300", "--synthetic", "1", "--num_queries", "64",
-            "--num_negatives", "32", "--k1", "1.0", "--base_lr", "0.01", "--graphs", str(graphs), "--graph_train", str(graphs)]
+            "--num_negatives", "32", "--k1", "1.0", "--base_lr", "0.01", "--graphs", str(graphs), "--graph_train", str(graphs), *extra]
     args = T.build_parser().parse_args(argv)
     args.patch_size = list(patch)
     st = T.ArcoStep2D(args, "cuda:0")
@@ -434,24 +434,31 @@ def test_default_trainer_keeps_the_reference_generator_sequence_without_the_pool
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("side_mode", [3, 4])
-def test_pass_concurrency_equals_the_single_stream_step(side_mode):
-    """(side_mode 4: the warped pass additionally starts before the main stream's row lists / bank appends and runs its OWN backward()
-    on the side stream before the heads and the InfoNCE are done.)  Round 4: the default step runs the teacher's grouped pass, the statistics-only pass and the warped student pass on a second
-    stream (train_arco_2d.TEACHER_SIDE = 3: forward AND backward of the warped pass beside the main pass's, parameter gradients in a
-    second flat buffer merged once).  From equal state, steps 1-6 (graphs captured at the third call, replayed afterwards) must give
-    the losses, weights, BatchNorm buffers and banks of the single-stream step (ARCO_TEACHER_SIDE=0) - the passes were independent
-    already, only their order in time changed."""
+@pytest.mark.parametrize("variant", ["default", "k2_0", "classmix"])
+def test_pass_concurrency_equals_the_single_stream_step(variant):
+    """The concurrent schedule (train_arco_2d.TEACHER_SIDE = 4, the default) against the single-stream step (0).  The default step runs
+    the statistics-only pass from the step's start, the teacher's grouped pass and the warped student pass on a second stream (forward
+    AND backward of the warped pass beside the main pass's, started before the main stream's row lists / bank appends, parameter
+    gradients in a second flat buffer merged once), and the image side of the mixing on a third.  From equal state, steps 1-6 (graphs
+    captured at the third call, replayed afterwards) must give the losses, weights, BatchNorm buffers and banks of the single-stream
+    step - the passes were independent already, only their order in time changed.
+    `k2_0`: no warped pass - the statistics pass and the image mixing beside the teacher only (what bench.py's k2_0 run times).
+    `classmix`: the masks are the pseudo-labels', so the mixing stays in line behind the teacher's first pass, while the statistics
+    pass and the warped pass stay on the side stream."""
+    extra = {"default": (), "k2_0": ("--k2", "0.0"), "classmix": ("--apply_aug", "classmix")}[variant]
+    side_mode, warped = 4, variant != "k2_0"
     from arco_amd import train_arco_2d as T
     b, patch, C = 2, (64, 64), 4
     seed_state = (fx.unet_state(21, 1, C), fx.fe_state(31), [fx.fe_state(32)["fea4.weight"], fx.fe_state(33)["fea4.weight"]])
     prev = T.TEACHER_SIDE
     try:
         T.TEACHER_SIDE = 0
-        st_a = _trainer(1, seed_state)
+        st_a = _trainer(1, seed_state, extra)
         T.TEACHER_SIDE = side_mode
-        st_b = _trainer(1, seed_state)
-        assert st_b._tps_side and not st_a._tps_side
+        st_b = _trainer(1, seed_state, extra)
+        assert st_a.args.k2 == st_b.args.k2 == (1.0 if warped else 0.0) and st_b.args.apply_aug == ("classmix" if variant == "classmix" else "cutmix")
+        if warped:
+            assert st_b._tps_side and not st_a._tps_side
         rs = np.random.RandomState(5)
         for it in range(6):
             l = torch.from_numpy(rs.uniform(size=(b, 1, *patch)).astype(np.float32)).cuda()
@@ -479,8 +486,9 @@ def test_pass_concurrency_equals_the_single_stream_step(side_mode):
                     np.testing.assert_allclose(vb.cpu().numpy(), va.cpu().numpy(), rtol=1e-4, atol=1e-6, err_msg=f"teacher {it} {k}")
             for ba, bb in zip(st_a.memobank, st_b.memobank):
                 np.testing.assert_allclose(bb[0].cpu().numpy(), ba[0].cpu().numpy(), rtol=1e-4, atol=1e-6)
-        assert st_b.s_train_tps.captured and st_b.s_train_tps.grad_views is not None
-        assert float(st_b.optimizer.flat_g2.abs().max()) == 0.0            # merged and cleared
+        if warped:
+            assert st_b.s_train_tps.captured and st_b.s_train_tps.grad_views is not None
+            assert float(st_b.optimizer.flat_g2.abs().max()) == 0.0            # merged and cleared
     finally:
         T.TEACHER_SIDE = prev
 

@@ -11,6 +11,8 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 lits = (sys.argv[2] if len(sys.argv) > 2 else "lits") == "lits"
 extra = sys.argv[3:]
 if os.environ.get("R3_PASS_SIDE"):
+    if os.environ["R3_PASS_SIDE"] not in ("0", "3"):
+        sys.exit("R3_PASS_SIDE: 0 (single-stream) or 3 (concurrent, the default)")
     T3.PASS_SIDE = int(os.environ["R3_PASS_SIDE"])
 sp, b, C = ((160, 160, 96), 1, 2) if lits else ((112, 112, 80), 2, 4)
 st = TC._make3d((["--act_dtype", "f16"] if lits else []) + extra, patch=sp, b=b, n_cls=C)

@@ -1,6 +1,6 @@
 """Which trainer is not reproducible?  From one snapshot of the state, the same step (same batch, same seeds) is executed again and
 again by the eager trainer and by the graph-replay trainer; each run's flat gradient is compared with that trainer's FIRST run.
-Head-backward atomics give ~1e-7; anything larger is a hazard.  python tools/debug/self_consistency.py [trials] [mode]"""
+Head-backward atomics give ~1e-7; anything larger is a hazard.  python tools/debug/self_consistency.py [trials] [TEACHER_SIDE: 0 | 4]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -9,6 +9,8 @@ import test_configs_at_size_gpu as TC
 from arco_amd import train_arco_2d as T, ops
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 if len(sys.argv) > 2:
+    if sys.argv[2] not in ("0", "4"):
+        sys.exit("TEACHER_SIDE: 0 (single-stream) or 4 (concurrent, the default)")
     T.TEACHER_SIDE = int(sys.argv[2])
 which = sys.argv[3] if len(sys.argv) > 3 else "eg"
 sts = {}

@@ -1,5 +1,5 @@
 """3-D twin of self_consistency.py: the same step from one snapshot, repeated; each run's flat gradient against the first run's.
-python tools/debug/self_consistency3d.py [trials] [PASS_SIDE] [lits]"""
+python tools/debug/self_consistency3d.py [trials] [PASS_SIDE: 0 | 3] [lits]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -7,6 +7,8 @@ import random, numpy as np, torch
 from arco_amd import train_arco_3d as T3, ops
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 if len(sys.argv) > 2:
+    if sys.argv[2] not in ("0", "3"):
+        sys.exit("PASS_SIDE: 0 (single-stream) or 3 (concurrent, the default)")
     T3.PASS_SIDE = int(sys.argv[2])
 lits = "lits" in sys.argv
 b = 1 if lits else 2
