@@ -167,6 +167,8 @@ _QUERIES = {   # plain host helpers returning sizes
     "arco_conv3d_fl_set": ([_I], _I),
     "arco_gemm_sp_set": ([_I, _L], _I),
     "arco_wgrad_ws_floats": ([_I, _I, _I, _L], _L),
+    "arco_wgrad_config": ([_I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _I, _I, _I, _P, _P, _P], _I),
+    "arco_wgrad_last_route": ([], _I),
     "arco_chan_stats_blocks": ([_L], _I),
     "arco_sel_state_bytes": ([], _L),
     "arco_sel_state_offset": ([_I], _L),

@@ -1200,42 +1200,28 @@ static void launch_hwgrad(const HWgradArgs& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(kern, grid, dim3(256), sh, st, a);
 }
 
-// dW (+)= weight gradient from f16 dZ / X; ws sized by arco_wgrad_ws_floats (same slab reservation as the fp32 kernels)
+// the slabs of the weight gradient from f16 dZ / X into ws (sized by arco_wgrad_ws_floats, same slab reservation as the fp32 kernels);
+// tile, grid and slab count are wgrad_plan's (igemm.hip), the caller sums the slabs
 int hwgrad_dispatch(const void* dZ, long ld_dz, int Cout, const void* in, long ld_in, int Cin, int taps, int NB, int D3, int H, int W,
-                    float* ws, float* dW, int accumulate, hipStream_t st) {
+                    float* ws, const WgradPlan& p, hipStream_t st) {
+  if (p.family != WG_F_HGRAD) return ARCO_ERR_UNSUPPORTED;
   HWgradArgs a{};
   a.dZ = reinterpret_cast<const _Float16*>(dZ); a.ldz = ld_dz; a.Cout = Cout;
   a.X = reinterpret_cast<const _Float16*>(in); a.ldx = ld_in; a.Cin = Cin;
   a.taps = taps; a.NB = NB; a.H = H; a.W = W; a.D3 = D3; a.M = (long)NB * H * W; a.partial = ws;
-  // (2-D 3x3: dZ rows of any width are staged element-wise when they are not whole 16-byte pieces - the U-Net's 19-class out_conv)
-  if ((Cin & 7) != 0 || (ld_in & 7) != 0 || ((ld_dz & 1) != 0 && taps != 9)) return ARCO_ERR_UNSUPPORTED;
-  long chunks;
+  a.CoutPad = p.CoutPad; a.CinPad = p.CinPad; a.n_tiles = p.n_tiles;
+  const dim3 grid((unsigned)p.slabs, (unsigned)p.ydim, (unsigned)p.zdim);
   if (taps >= 9) {
-    const int hco = Cout > 16 ? 32 : 16, hci = Cin > 16 ? 32 : 16;
-    a.CoutPad = (Cout + hco - 1) / hco * hco; a.CinPad = (Cin + hci - 1) / hci * hci;
-    a.n_tiles = NB * ((H + 7) / 8) * ((W + 15) / 16);
-    const int zdim = taps / 9, ydim = (a.CoutPad / hco) * (a.CinPad / hci);
-    static const long target = getenv("ARCO_HWGRAD_TARGET") ? atol(getenv("ARCO_HWGRAD_TARGET")) : 512;
-    chunks = target / ((long)zdim * ydim); if (chunks > a.n_tiles) chunks = a.n_tiles; if (chunks < 1) chunks = 1;
-    const dim3 grid((unsigned)chunks, ydim, zdim);
-    if (hco == 32 && hci == 32) launch_hwgrad<2, 2, 9>(a, grid, st);
-    else if (hco == 32) launch_hwgrad<2, 1, 9>(a, grid, st);
-    else if (hci == 32) launch_hwgrad<1, 2, 9>(a, grid, st);
+    if (p.cob == 32 && p.cib == 32) launch_hwgrad<2, 2, 9>(a, grid, st);
+    else if (p.cob == 32) launch_hwgrad<2, 1, 9>(a, grid, st);
+    else if (p.cib == 32) launch_hwgrad<1, 2, 9>(a, grid, st);
     else launch_hwgrad<1, 1, 9>(a, grid, st);
   } else {
-    const int co_b = Cout >= 64 ? 64 : (Cout > 16 ? 32 : 16), ci_b = Cin >= 64 ? 64 : (Cin > 16 ? 32 : 16);
-    a.CoutPad = (Cout + co_b - 1) / co_b * co_b; a.CinPad = (Cin + ci_b - 1) / ci_b * ci_b;
-    a.n_tiles = (int)((a.M + 127) / 128);
-    const long ydim = (long)(a.CoutPad / co_b) * (a.CinPad / ci_b);
-    static const long target1 = getenv("ARCO_HWGRAD1_TARGET") ? atol(getenv("ARCO_HWGRAD1_TARGET")) : 512;
-    chunks = target1 / ydim; if (chunks < 1) chunks = 1; if (chunks > a.n_tiles) chunks = a.n_tiles;
-    const dim3 grid((unsigned)chunks, (unsigned)ydim, 1);
-#define HW1(CO, CI) if (co_b == 16 * CO && ci_b == 16 * CI) launch_hwgrad<CO, CI, 1>(a, grid, st)
+#define HW1(CO, CI) if (p.cob == 16 * CO && p.cib == 16 * CI) launch_hwgrad<CO, CI, 1>(a, grid, st)
     HW1(4, 4); else HW1(4, 2); else HW1(4, 1); else HW1(2, 4); else HW1(2, 2); else HW1(2, 1); else HW1(1, 4); else HW1(1, 2); else HW1(1, 1);
 #undef HW1
   }
-  launch_wgrad_reduce(st, ws, (int)chunks, taps, a.CoutPad, a.CinPad, Cout, Cin, dW, accumulate);
-  return arco_launch_status();
+  return ARCO_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

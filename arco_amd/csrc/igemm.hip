@@ -1957,13 +1957,20 @@ __global__ __launch_bounds__(512) void wgrad_reduce4_kernel(const float* __restr
     }
   }
 }
+// which slab reduction follows a launch of `chunks` slabs: 1 wgrad_reduce_kernel<64,8>, 2 wgrad_reduce_kernel<16,32>, 3 wgrad_reduce4_kernel
+int wgrad_reduce_kind(long chunks, int taps, int CinPad, int Cout, int Cin) {
+  const long tot = (long)Cout * Cin * taps;
+  static const bool v4 = !(getenv("ARCO_WGRAD_REDUCE4") && atoi(getenv("ARCO_WGRAD_REDUCE4")) == 0);
+  if (v4 && chunks > 16 && (Cin & 3) == 0 && (CinPad & 3) == 0 && tot >= 64 * 64) return 3;
+  return chunks > 16 ? 2 : 1;
+}
 void launch_wgrad_reduce(hipStream_t st, const float* ws, int chunks, int taps, int CoutPad, int CinPad, int Cout, int Cin,
                                 float* dW, int accumulate) {
   const long tot = (long)Cout * Cin * taps;
-  static const bool v4 = !(getenv("ARCO_WGRAD_REDUCE4") && atoi(getenv("ARCO_WGRAD_REDUCE4")) == 0);
-  if (v4 && chunks > 16 && (Cin & 3) == 0 && (CinPad & 3) == 0 && tot >= 64 * 64)
+  const int kind = wgrad_reduce_kind(chunks, taps, CinPad, Cout, Cin);
+  if (kind == 3)
     hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)((tot / 4 + 15) / 16)), dim3(512), 0, st, ws, chunks, taps, CoutPad, CinPad, Cout, Cin, dW, accumulate);
-  else if (chunks > 16)
+  else if (kind == 2)
     hipLaunchKernelGGL((wgrad_reduce_kernel<16, 32>), dim3((tot + 15) / 16), dim3(512), 0, st, ws, chunks, taps, CoutPad, CinPad, Cout, Cin, dW, accumulate);
   else
     hipLaunchKernelGGL((wgrad_reduce_kernel<64, 8>), dim3((tot + 63) / 64), dim3(512), 0, st, ws, chunks, taps, CoutPad, CinPad, Cout, Cin, dW, accumulate);
@@ -2034,6 +2041,7 @@ __global__ void transpose2d_kernel(const float* __restrict__ x, long ldx, int ro
 }
 
 thread_local int arco_last_route = 0;
+thread_local int arco_wgrad_route = 0;
 
 extern "C" {
 
@@ -2345,6 +2353,148 @@ int arco_conv_wgrad(const float* dZ, long ld_dz, int Cout, const float* in, long
   return arco_conv3d_wgrad(dZ, ld_dz, Cout, in, ld_in, Cin, taps, NB, 1, H, W, ws, dW, accumulate, 0, stream);
 }
 
+}  // extern "C"
+
+// ---- the weight-gradient route: kernel, tile, flat or rectangular, slab count and reduction, in pure host code ------------------------
+static int wgrad_plan_finish(WgradPlan& p, int tapform, int fam, int var, int cob, int cib, long slabs, int taps, int Cout, int Cin, long M) {
+  p.family = fam; p.cob = cob; p.cib = cib;
+  p.slab_floats = (long)taps * p.CoutPad * p.CinPad;
+  // one slab per workgroup, and never more slabs than arco_wgrad_ws_floats reserves for the same (Cout, Cin, taps, M): its bound
+  // ceil(M / 128) * 4 + 64 is below the tile count of a batch of many small planes (200 maps of 4 x 4: 200 tiles, 164 slabs).  Every
+  // kernel strides its tiles by gridDim.x, so fewer workgroups compute the same sums.
+  const long reserved = arco_wgrad_ws_floats(Cout, Cin, taps, M) / p.slab_floats;
+  if (slabs < 1) slabs = 1;
+  if (slabs > reserved) slabs = reserved;
+  if (slabs < 1) return ARCO_ERR_UNSUPPORTED;
+  p.slabs = slabs;
+  p.reduce = wgrad_reduce_kind(slabs, taps, p.CinPad, Cout, Cin);
+  p.route = tapform * 1000000 + fam * 100000 + var * 10000 + cob * 100 + cib;
+  return ARCO_OK;
+}
+
+int wgrad_plan(int entry, int taps, int NV, int D3, int H, int W, int Cin, int Cout, long ld_dz, long ld_in, int mma, bool pro_on,
+               int pro_groups, bool aligned16, WgradPlan& p) {
+  p = WgradPlan{};
+  const int NB = NV * D3;
+  const long M = (long)NB * H * W;
+  p.ydim = p.zdim = 1;
+  if (entry == 1) {      // arco_conv3x3_image_wgrad_h: f16 dZ of 16 channels against the fp32 image of Cin <= 4 channels
+    if (taps != 9 || Cout != 16 || (ld_dz & 7) != 0 || !aligned16) return ARCO_ERR_UNSUPPORTED;
+    p.CoutPad = 16; p.CinPad = 16;
+    const long tiles = (long)NB * ((H + 15) / 16) * ((W + 15) / 16);
+    p.n_tiles = (int)tiles;
+    return wgrad_plan_finish(p, 9, WG_F_HIMAGE, 0, 16, Cin, tiles < 512 ? tiles : 512, taps, Cout, Cin, M);
+  }
+  if (pro_on) {          // arco_conv3d_wgrad_pro: (the 3x3x3 consumer-side activation exists in the forward kernel only: gradient-free passes)
+    if (taps != 9) return ARCO_ERR_UNSUPPORTED;
+    if (!arco_conv_pro_ok(taps, NV, D3, H, W, Cin, Cout, ld_in, mma, pro_groups) || (ld_dz & 3) != 0) return ARCO_ERR_UNSUPPORTED;
+  }
+  if (mma == 4 && !(taps >= 9 && Cin == 1)) {     // f16 activation storage (dZ and in are f16; the first layer's input volume is fp32): conv_h.hip
+    // (2-D 3x3: dZ rows of any width are staged element-wise when they are not whole 16-byte pieces - the U-Net's 19-class out_conv)
+    if ((Cin & 7) != 0 || (ld_in & 7) != 0 || ((ld_dz & 1) != 0 && taps != 9)) return ARCO_ERR_UNSUPPORTED;
+    if (taps >= 9) {
+      const int hco = Cout > 16 ? 32 : 16, hci = Cin > 16 ? 32 : 16;
+      p.CoutPad = (Cout + hco - 1) / hco * hco; p.CinPad = (Cin + hci - 1) / hci * hci;
+      p.n_tiles = NB * ((H + 7) / 8) * ((W + 15) / 16);
+      p.zdim = taps / 9; p.ydim = (p.CoutPad / hco) * (p.CinPad / hci);
+      static const long target = getenv("ARCO_HWGRAD_TARGET") ? atol(getenv("ARCO_HWGRAD_TARGET")) : 512;
+      long chunks = target / ((long)p.zdim * p.ydim); if (chunks > p.n_tiles) chunks = p.n_tiles;
+      return wgrad_plan_finish(p, 9, WG_F_HGRAD, 0, hco, hci, chunks, taps, Cout, Cin, M);
+    }
+    const int co_b = Cout >= 64 ? 64 : (Cout > 16 ? 32 : 16), ci_b = Cin >= 64 ? 64 : (Cin > 16 ? 32 : 16);
+    p.CoutPad = (Cout + co_b - 1) / co_b * co_b; p.CinPad = (Cin + ci_b - 1) / ci_b * ci_b;
+    p.n_tiles = (int)((M + 127) / 128);
+    p.ydim = (p.CoutPad / co_b) * (p.CinPad / ci_b);
+    static const long target1 = getenv("ARCO_HWGRAD1_TARGET") ? atol(getenv("ARCO_HWGRAD1_TARGET")) : 512;
+    long chunks = target1 / p.ydim; if (chunks < 1) chunks = 1; if (chunks > p.n_tiles) chunks = p.n_tiles;
+    return wgrad_plan_finish(p, 1, WG_F_HGRAD, 0, co_b, ci_b, chunks, taps, Cout, Cin, M);
+  }
+  const int amma = mma >= 3 ? mma : ((taps == 27 && mma) ? 2 : 0);   // 1 / 2: bf16 operands (gradients: range); 3: split-bf16 (fp32-accurate)
+  const int co_b = Cout >= 64 ? 64 : (Cout > 16 ? 32 : 16), ci_b = Cin >= 64 ? 64 : (Cin > 16 ? 32 : 16);
+  p.CoutPad = (Cout + co_b - 1) / co_b * co_b; p.CinPad = (Cin + ci_b - 1) / ci_b * ci_b;
+  p.n_tiles = taps >= 9 ? NB * ((H + 7) / 8) * ((W + 15) / 16) : (int)((M + 127) / 128);
+  if (taps >= 9 && Cin == 1 && Cout <= 16 && (Cout & 3) == 0 && (ld_dz & 3) == 0) {   // one-channel input (first layer of both nets): taps as M
+    if (pro_on) return ARCO_ERR_UNSUPPORTED;
+    p.CoutPad = 16; p.CinPad = 16;
+    const long tiles = (long)NB * ((H + 15) / 16) * ((W + 15) / 16);
+    p.n_tiles = (int)tiles;
+    return wgrad_plan_finish(p, 9, WG_F_IMAGE, taps / 9, 16, 16, tiles < 512 ? tiles : 512, taps, Cout, Cin, M);
+  }
+  // f16 dZ against the one-channel fp32 volume exists in wgrad_image3d_kernel only: the kernels below would read the f16 rows as fp32
+  if (amma == 4) return ARCO_ERR_UNSUPPORTED;
+  if (taps >= 9) {       // spatial kernels: all taps of a plane per block, operands staged once (halo in LDS)
+    const int hco = Cout > 16 ? 32 : 16, hci = Cin > 16 ? 32 : 16;
+    p.CoutPad = (Cout + hco - 1) / hco * hco; p.CinPad = (Cin + hci - 1) / hci * hci;
+    // narrow planes (W not a multiple of 16): flat-position tiles for the fp32 / reduced-precision kernels.  In split-bf16 mode
+    // the rectangular 8 x 16 tiles of wgrad_split_kernel are taken instead, ragged last column of tiles and all (W = 40: 17 %
+    // of the MFMA rows idle, W = 20 / 10: 37 %) - six bf16 MFMAs per 32 pixels still beat eight fp32 MFMAs per 16 by more than
+    // that (A/B knob ARCO_WGRAD_FLAT_SPLIT=0: round 2's choice, the fp32 flat-tile kernel)
+    static const int flat_split = getenv("ARCO_WGRAD_FLAT_SPLIT") ? atoi(getenv("ARCO_WGRAD_FLAT_SPLIT")) : 1;
+    const bool split_ok = amma == 3 && (Cout & 3) == 0 && (Cin & 3) == 0 && (ld_dz & 3) == 0 && (ld_in & 3) == 0;
+    p.flat = (W & 15) != 0 && W + 2 <= IGEMM_FLAT_WPMAX && !(split_ok && flat_split && W >= 10);
+    if (p.flat) p.n_tiles = NB * ((H * (W + 2) + 127) / 128);
+    p.zdim = taps / 9; p.ydim = (p.CoutPad / hco) * (p.CinPad / hci);
+    // 32x32 blocks run persistent (2 workgroups per CU, several tiles each); the others one slab per ~tile
+    // (16 x 32 blocks of the split kernel: 60.7 KB of LDS, two per CU as well - 768 left a third round at half occupancy)
+    static const long target_env = getenv("ARCO_WGRAD_TARGET") ? atol(getenv("ARCO_WGRAD_TARGET")) : 0;     // A/B knob (<= the defaults: the slab reservation)
+    const long target = target_env > 0 ? target_env : ((hci == 32 && (hco == 32 || amma == 3)) ? 512 : 768);
+    long chunks = target / ((long)p.zdim * p.ydim); if (chunks > p.n_tiles) chunks = p.n_tiles;
+    const bool split = split_ok && !p.flat;
+    if (pro_on && !split) return ARCO_ERR_UNSUPPORTED;
+    if (split) return wgrad_plan_finish(p, 9, WG_F_SPLIT, pro_on ? 1 : 0, hco, hci, chunks, taps, Cout, Cin, M);
+    p.bf16 = amma == 2;
+    return wgrad_plan_finish(p, 9, WG_F_HALO, (p.flat ? 1 : 0) + (p.bf16 ? 2 : 0), hco, hci, chunks, taps, Cout, Cin, M);
+  }
+  {   // wide 1x1 gradients over many pixels: 128 x 128 blocks, one workgroup per CU (wgrad_q_kernel); A/B knob ARCO_WGRAD_Q=0
+    static const int wq = getenv("ARCO_WGRAD_Q") ? atoi(getenv("ARCO_WGRAD_Q")) : 1;
+    const int cop = (Cout + 127) / 128 * 128, cip = (Cin + 127) / 128 * 128;
+    const long yzq = (long)(cop / 128) * (cip / 128);
+    const long reserved = arco_wgrad_ws_floats(Cout, Cin, taps, M);
+    long chq = 256 / yzq; if (chq < 1) chq = 1; if (chq > p.n_tiles) chq = p.n_tiles;
+    if (wq && taps == 1 && Cout >= 192 && Cin >= 192 && M >= 32768 && (Cout & 3) == 0 && (Cin & 3) == 0 &&
+        (ld_dz & 3) == 0 && (ld_in & 3) == 0 && aligned16 && chq * cop * cip <= reserved) {
+      p.CoutPad = cop; p.CinPad = cip;
+      p.ydim = cop / 128; p.zdim = cip / 128;
+      static const int tp = getenv("ARCO_WGRAD_Q_TP") ? atoi(getenv("ARCO_WGRAD_Q_TP")) : 64;
+      if (tp == 64) {
+        p.n_tiles = (int)((M + 63) / 64);
+        long ch2 = 512 / yzq; if (ch2 < 1) ch2 = 1; if (ch2 > p.n_tiles) ch2 = p.n_tiles;
+        if (ch2 * cop * cip <= reserved) chq = ch2;
+      }
+      return wgrad_plan_finish(p, 1, WG_F_Q, 0, 0, tp == 64 ? 64 : 128, chq, taps, Cout, Cin, M);
+    }
+  }
+  p.ydim = p.CoutPad / co_b; p.zdim = (p.CinPad / ci_b) * taps;
+  const long yz = (long)p.ydim * p.zdim;
+  static const long target1 = getenv("ARCO_WGRAD1_TARGET") ? atol(getenv("ARCO_WGRAD1_TARGET")) : 512;   // two resident workgroups per CU, 6-13 tiles each (2048: 3 tiles each, a third of them behind an exposed first fetch; 4x the slabs)
+  long chunks = target1 / yz; if (chunks < 1) chunks = 1; if (chunks > p.n_tiles) chunks = p.n_tiles;
+  return wgrad_plan_finish(p, 1, WG_F_GEMM, 0, co_b, ci_b, chunks, taps, Cout, Cin, M);
+}
+
+extern "C" {
+
+// Test-facing: the id of the kernel that the most recent weight-gradient launch of this thread took (arco_conv_wgrad, arco_conv3d_wgrad(_pro),
+// arco_conv3x3_image_wgrad_h, the f16 kernels of conv_h.hip included); 0 before the first launch and after a call that found no kernel
+// (ARCO_ERR_UNSUPPORTED); a call rejected with ARCO_ERR_ARG leaves it unchanged.  Host side only: one thread-local store per launch.
+int arco_wgrad_last_route(void) { return arco_wgrad_route; }
+
+// Query: the route wgrad_plan chooses - the function the launch itself calls.  Returns the kernel id or ARCO_ERR_UNSUPPORTED;
+// *slabs = workgroups along x = slabs written to ws, *slab_floats = floats per slab, *reduce = 1 wgrad_reduce_kernel<64,8>,
+// 2 wgrad_reduce_kernel<16,32>, 3 wgrad_reduce4_kernel (each may be NULL).
+int arco_wgrad_config(int entry, int taps, int NV, int D3, int H, int W, int Cin, int Cout, long ld_dz, long ld_in, int mma,
+                      int pro_groups, int aligned16, long* slabs, long* slab_floats, int* reduce) {
+  ARCO_CHECK_ARG((entry == 0 || entry == 1) && (taps == 1 || taps == 9 || taps == 27) && mma >= 0 && mma <= 4 && NV > 0 && D3 > 0 && H > 0 &&
+                 W > 0 && Cin > 0 && Cout > 0 && ld_dz >= Cout && ld_in >= Cin && pro_groups >= 0 &&
+                 (entry == 0 || (Cin <= 4 && D3 == 1 && taps == 9)));
+  WgradPlan p;
+  const int rc = wgrad_plan(entry, taps, NV, D3, H, W, Cin, Cout, ld_dz, ld_in, mma, pro_groups > 0, pro_groups, aligned16 != 0, p);
+  if (rc != ARCO_OK) return rc;
+  if (slabs) *slabs = p.slabs;
+  if (slab_floats) *slab_floats = p.slab_floats;
+  if (reduce) *reduce = p.reduce;
+  return p.route;
+}
+
 static int conv3d_wgrad_impl(const float* dZ, long ld_dz, int Cout, const float* in, long ld_in, int Cin, int taps, int NV,
                              int D3, int H, int W, float* ws, float* dW, int accumulate, int mma, const ArcoActPro* pro, void* stream);
 int arco_conv3d_wgrad(const float* dZ, long ld_dz, int Cout, const float* in, long ld_in, int Cin, int taps, int NV,
@@ -2356,56 +2506,44 @@ int arco_conv3d_wgrad_pro(const float* dZ, long ld_dz, int Cout, const float* in
                           int D3, int H, int W, float* ws, float* dW, int accumulate, int mma, const ArcoActPro* pro, void* stream) {
   ARCO_CHECK_ARG(pro && pro->mean && pro->istd && pro->gamma && pro->beta && pro->groups >= 1 && (pro->drop_mode == 0 || pro->drop_mode == 1) &&
                  pro->p >= 0.f && pro->p < 1.f);
-  if (taps != 9) return ARCO_ERR_UNSUPPORTED;        // (the 3x3x3 consumer-side activation exists in the forward kernel only: gradient-free passes)
-  if (!arco_conv_pro_ok(taps, NV, D3, H, W, Cin, Cout, ld_in, mma, pro->groups) || (ld_dz & 3) != 0) return ARCO_ERR_UNSUPPORTED;
   return conv3d_wgrad_impl(dZ, ld_dz, Cout, in, ld_in, Cin, taps, NV, D3, H, W, ws, dW, accumulate, mma, pro, stream);
 }
 
 static int conv3d_wgrad_impl(const float* dZ, long ld_dz, int Cout, const float* in, long ld_in, int Cin, int taps, int NV,
                              int D3, int H, int W, float* ws, float* dW, int accumulate, int mma, const ArcoActPro* pro, void* stream) {
+  ARCO_CHECK_ARG(dZ && in && ws && dW && (taps == 1 || taps == 9 || taps == 27) && mma >= 0 && mma <= 4 && Cout > 0 && Cin > 0 && NV > 0 &&
+                 D3 > 0 && H > 0 && W > 0 && ld_dz >= Cout && ld_in >= Cin && (accumulate == 0 || accumulate == 1));
   const int NB = NV * D3;
-  ARCO_CHECK_ARG(dZ && in && ws && dW && (taps == 1 || taps == 9 || taps == 27) && mma >= 0 && mma <= 4);
-  if (mma == 4 && !(taps >= 9 && Cin == 1))      // f16 activation storage (dZ and in are f16; the first layer's input volume is fp32)
-    return hwgrad_dispatch(dZ, ld_dz, Cout, in, ld_in, Cin, taps, NB, D3, H, W, ws, dW, accumulate, as_stream(stream));
+  arco_note_wgrad_route(0);
+  WgradPlan p;
+  const bool aligned16 = (reinterpret_cast<uintptr_t>(dZ) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+  const int rc = wgrad_plan(0, taps, NV, D3, H, W, Cin, Cout, ld_dz, ld_in, mma, pro != nullptr, pro ? pro->groups : 0, aligned16, p);
+  if (rc != ARCO_OK) return rc;
+  hipStream_t st = as_stream(stream);
+  if (p.family == WG_F_HGRAD) {
+    const int r = hwgrad_dispatch(dZ, ld_dz, Cout, in, ld_in, Cin, taps, NB, D3, H, W, ws, p, as_stream(stream));
+    if (r != ARCO_OK) return r;
+    arco_note_wgrad_route(p.route);
+    launch_wgrad_reduce(st, ws, (int)p.slabs, taps, p.CoutPad, p.CinPad, Cout, Cin, dW, accumulate);
+    return arco_launch_status();
+  }
   WgradArgs a{};
-  a.D3 = D3; a.mma = mma >= 3 ? mma : ((taps == 27 && mma) ? 2 : 0);   // 1 / 2: bf16 operands (gradients: range); 3: split-bf16 (fp32-accurate)
+  a.D3 = D3; a.mma = mma >= 3 ? mma : ((taps == 27 && mma) ? 2 : 0);
   a.dZ = dZ; a.ldz = ld_dz; a.Cout = Cout; a.Ain = in; a.lda = ld_in; a.Cin = Cin; a.taps = taps;
   a.NB = NB; a.H = H; a.W = W; a.M = (long)NB * H * W; a.partial = ws;
   static const int abl = getenv("ARCO_WGRAD_ABL") ? atoi(getenv("ARCO_WGRAD_ABL")) : 0;
   a.abl = abl;
   if (pro) a.pro = *pro;
-  const int co_b = Cout >= 64 ? 64 : (Cout > 16 ? 32 : 16), ci_b = Cin >= 64 ? 64 : (Cin > 16 ? 32 : 16);
-  a.CoutPad = (Cout + co_b - 1) / co_b * co_b; a.CinPad = (Cin + ci_b - 1) / ci_b * ci_b;
-  a.n_tiles = taps >= 9 ? NB * ((H + 7) / 8) * ((W + 15) / 16) : (int)((a.M + 127) / 128);
-  hipStream_t st = as_stream(stream);
-  if (taps >= 9 && Cin == 1 && Cout <= 16 && (Cout & 3) == 0 && (ld_dz & 3) == 0) {   // one-channel input (first layer of both nets): taps as M
-    a.CoutPad = 16; a.CinPad = 16;
+  a.CoutPad = p.CoutPad; a.CinPad = p.CinPad; a.n_tiles = p.n_tiles;
+  const long chunks = p.slabs;
+  if (p.family == WG_F_IMAGE) {
     if (taps == 9) a.D3 = 1;
-    const long tiles = (long)NB * ((H + 15) / 16) * ((W + 15) / 16);
-    const long chunks = tiles < 512 ? tiles : 512;              // <= the slab count arco_wgrad_ws_floats reserves
     if (taps == 27) hipLaunchKernelGGL(wgrad_image3d_kernel<3>, dim3((unsigned)chunks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(wgrad_image3d_kernel<1>, dim3((unsigned)chunks), dim3(256), 0, st, a);
-    launch_wgrad_reduce(st, ws, (int)chunks, taps, a.CoutPad, a.CinPad, Cout, Cin, dW, accumulate);
-    return arco_launch_status();
-  }
-  if (taps >= 9) {       // spatial kernels: all taps of a plane per block, operands staged once (halo in LDS)
-    const int hco = Cout > 16 ? 32 : 16, hci = Cin > 16 ? 32 : 16;
-    a.CoutPad = (Cout + hco - 1) / hco * hco; a.CinPad = (Cin + hci - 1) / hci * hci;
-    // narrow planes (W not a multiple of 16): flat-position tiles for the fp32 / reduced-precision kernels.  In split-bf16 mode
-    // the rectangular 8 x 16 tiles of wgrad_split_kernel are taken instead, ragged last column of tiles and all (W = 40: 17 %
-    // of the MFMA rows idle, W = 20 / 10: 37 %) - six bf16 MFMAs per 32 pixels still beat eight fp32 MFMAs per 16 by more than
-    // that (A/B knob ARCO_WGRAD_FLAT_SPLIT=0: round 2's choice, the fp32 flat-tile kernel)
-    static const int flat_split = getenv("ARCO_WGRAD_FLAT_SPLIT") ? atoi(getenv("ARCO_WGRAD_FLAT_SPLIT")) : 1;
-    const bool split_ok = a.mma == 3 && (Cout & 3) == 0 && (Cin & 3) == 0 && (ld_dz & 3) == 0 && (ld_in & 3) == 0;
-    const bool flat = (W & 15) != 0 && W + 2 <= IGEMM_FLAT_WPMAX && !(split_ok && flat_split && W >= 10);
-    if (flat) a.n_tiles = NB * ((H * (W + 2) + 127) / 128);
-    const int zdim = taps / 9, ydim = (a.CoutPad / hco) * (a.CinPad / hci);
-    // 32x32 blocks run persistent (2 workgroups per CU, several tiles each); the others one slab per ~tile
-    // (16 x 32 blocks of the split kernel: 60.7 KB of LDS, two per CU as well - 768 left a third round at half occupancy)
-    static const long target_env = getenv("ARCO_WGRAD_TARGET") ? atol(getenv("ARCO_WGRAD_TARGET")) : 0;     // A/B knob (<= the defaults: the slab reservation)
-    const long target = target_env > 0 ? target_env : ((hci == 32 && (hco == 32 || a.mma == 3)) ? 512 : 768);
-    long chunks = target / ((long)zdim * ydim); if (chunks > a.n_tiles) chunks = a.n_tiles; if (chunks < 1) chunks = 1;
-    dim3 hgrid((unsigned)chunks, ydim, zdim);
+  } else if (p.family == WG_F_HALO || p.family == WG_F_SPLIT) {
+    const bool flat = p.flat;
+    const int hco = p.cob, hci = p.cib;
+    dim3 hgrid((unsigned)chunks, p.ydim, p.zdim);
 #define WH(COB, CIB)                                                                              \
     do {                                                                                          \
       constexpr int LZ = (COB % 32 == 0) ? COB + 16 : COB, LA = (CIB % 32 == 0) ? CIB + 16 : CIB; \
@@ -2422,7 +2560,6 @@ static int conv3d_wgrad_impl(const float* dZ, long ld_dz, int Cout, const float*
       } else if (a.mma == 2) hipLaunchKernelGGL((wgrad_halo2_kernel<COB, CIB, false, 2>), hgrid, dim3(256), sh, st, a); \
       else hipLaunchKernelGGL((wgrad_halo2_kernel<COB, CIB>), hgrid, dim3(256), sh, st, a);       \
     } while (0)
-    const bool split = a.mma == 3 && !flat && (Cout & 3) == 0 && (Cin & 3) == 0 && (ld_dz & 3) == 0 && (ld_in & 3) == 0;
 #define WS(COB, CIB)                                                                              \
     do {                                                                                          \
       size_t sh = (size_t)(3 * COB * ARCO_WG_CSZ + 3 * CIB * ARCO_WG_CSX) * 4; const size_t rd = (size_t)4 * 9 * 256 * 4; \
@@ -2436,8 +2573,7 @@ static int conv3d_wgrad_impl(const float* dZ, long ld_dz, int Cout, const float*
       } else                                                                                      \
       hipLaunchKernelGGL((wgrad_split_kernel<COB, CIB>), hgrid, dim3(256), sh, st, a);            \
     } while (0)
-    if (pro && !split) return ARCO_ERR_UNSUPPORTED;
-    if (split) {
+    if (p.family == WG_F_SPLIT) {
       if (hco == 32 && hci == 32) WS(32, 32);
       else if (hco == 32 && hci == 16) WS(32, 16);
       else if (hco == 16 && hci == 32) WS(16, 32);
@@ -2449,68 +2585,50 @@ static int conv3d_wgrad_impl(const float* dZ, long ld_dz, int Cout, const float*
     else WH(16, 16);
 #undef WS
 #undef WH
-    launch_wgrad_reduce(st, ws, (int)chunks, taps, a.CoutPad, a.CinPad, Cout, Cin, dW, accumulate);
-    return arco_launch_status();
-  }
-  {   // wide 1x1 gradients over many pixels: 128 x 128 blocks, one workgroup per CU (wgrad_q_kernel); A/B knob ARCO_WGRAD_Q=0
-    static const int wq = getenv("ARCO_WGRAD_Q") ? atoi(getenv("ARCO_WGRAD_Q")) : 1;
-    const int cop = (Cout + 127) / 128 * 128, cip = (Cin + 127) / 128 * 128;
-    const long yzq = (long)(cop / 128) * (cip / 128);
-    long chq = 256 / yzq; if (chq < 1) chq = 1; if (chq > a.n_tiles) chq = a.n_tiles;
-    if (wq && taps == 1 && a.mma != 4 && Cout >= 192 && Cin >= 192 && a.M >= 32768 && (Cout & 3) == 0 && (Cin & 3) == 0 &&
-        (ld_dz & 3) == 0 && (ld_in & 3) == 0 && (reinterpret_cast<uintptr_t>(dZ) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
-        chq * cop * cip <= arco_wgrad_ws_floats(Cout, Cin, taps, a.M)) {
-      a.CoutPad = cop; a.CinPad = cip;
-      static const int tp = getenv("ARCO_WGRAD_Q_TP") ? atoi(getenv("ARCO_WGRAD_Q_TP")) : 64;
-      if (tp == 64) {
-        a.n_tiles = (int)((a.M + 63) / 64);
-        long ch2 = 512 / yzq; if (ch2 < 1) ch2 = 1; if (ch2 > a.n_tiles) ch2 = a.n_tiles;
-        if (ch2 * cop * cip <= arco_wgrad_ws_floats(Cout, Cin, taps, a.M)) chq = ch2;
-        constexpr int shq = 64 * (2 * (128 + WGRAD1_PAD)) * 4;
-        static unsigned long long attr_q = 0;
-        if (arco_first_on_device(attr_q)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_q_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, shq); }
-        hipLaunchKernelGGL(wgrad_q_kernel<64>, dim3((unsigned)chq, cop / 128, cip / 128), dim3(256), shq, st, a);
-      } else {
-        constexpr int shq = 128 * (2 * (128 + WGRAD1_PAD)) * 4;
-        static unsigned long long attr_q = 0;
-        if (arco_first_on_device(attr_q)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_q_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, shq); }
-        hipLaunchKernelGGL(wgrad_q_kernel<128>, dim3((unsigned)chq, cop / 128, cip / 128), dim3(256), shq, st, a);
-      }
-      launch_wgrad_reduce(st, ws, (int)chq, taps, a.CoutPad, a.CinPad, Cout, Cin, dW, accumulate);
-      return arco_launch_status();
+  } else if (p.family == WG_F_Q) {
+    if (p.cib == 64) {
+      constexpr int shq = 64 * (2 * (128 + WGRAD1_PAD)) * 4;
+      static unsigned long long attr_q = 0;
+      if (arco_first_on_device(attr_q)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_q_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, shq); }
+      hipLaunchKernelGGL(wgrad_q_kernel<64>, dim3((unsigned)chunks, p.ydim, p.zdim), dim3(256), shq, st, a);
+    } else {
+      constexpr int shq = 128 * (2 * (128 + WGRAD1_PAD)) * 4;
+      static unsigned long long attr_q = 0;
+      if (arco_first_on_device(attr_q)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_q_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, shq); }
+      hipLaunchKernelGGL(wgrad_q_kernel<128>, dim3((unsigned)chunks, p.ydim, p.zdim), dim3(256), shq, st, a);
     }
-  }
-  const long yz = (long)(a.CoutPad / co_b) * (a.CinPad / ci_b) * taps;
-  static const long target1 = getenv("ARCO_WGRAD1_TARGET") ? atol(getenv("ARCO_WGRAD1_TARGET")) : 512;   // two resident workgroups per CU, 6-13 tiles each (2048: 3 tiles each, a third of them behind an exposed first fetch; 4x the slabs)
-  long chunks = target1 / yz; if (chunks < 1) chunks = 1; if (chunks > a.n_tiles) chunks = a.n_tiles;
-  dim3 grid((unsigned)chunks, a.CoutPad / co_b, (a.CinPad / ci_b) * taps);
+  } else {
+    const int co_b = p.cob, ci_b = p.cib;
+    dim3 grid((unsigned)chunks, p.ydim, p.zdim);
 #define WG(COB, CIB)                                                                              \
-  do {                                                                                            \
-    constexpr int LZ = (COB % 32 == 0) ? COB + WGRAD1_PAD : COB, LA = (CIB % 32 == 0) ? CIB + WGRAD1_PAD : CIB;   \
-    size_t sh = (size_t)128 * (LZ + LA) * 4; const size_t rd = (size_t)4 * COB * CIB * 4;         \
-    if (sh < rd) sh = rd;                                                                         \
-    auto kern = wgrad_kernel<COB, CIB>;                                                           \
-    static unsigned long long attr_set = 0;   /* once per instantiation: not legal inside a stream capture */ \
-    if (sh > 64 * 1024 && arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); } \
-    hipLaunchKernelGGL(kern, grid, dim3(256), sh, st, a);                                         \
-  } while (0)
-  if (co_b == 64 && ci_b == 64) WG(64, 64);
-  else if (co_b == 64 && ci_b == 32) WG(64, 32);
-  else if (co_b == 64 && ci_b == 16) WG(64, 16);
-  else if (co_b == 32 && ci_b == 64) WG(32, 64);
-  else if (co_b == 32 && ci_b == 32) WG(32, 32);
-  else if (co_b == 32 && ci_b == 16) WG(32, 16);
-  else if (co_b == 16 && ci_b == 64) WG(16, 64);
-  else if (co_b == 16 && ci_b == 32) WG(16, 32);
-  else WG(16, 16);
+    do {                                                                                            \
+      constexpr int LZ = (COB % 32 == 0) ? COB + WGRAD1_PAD : COB, LA = (CIB % 32 == 0) ? CIB + WGRAD1_PAD : CIB;   \
+      size_t sh = (size_t)128 * (LZ + LA) * 4; const size_t rd = (size_t)4 * COB * CIB * 4;         \
+      if (sh < rd) sh = rd;                                                                         \
+      auto kern = wgrad_kernel<COB, CIB>;                                                           \
+      static unsigned long long attr_set = 0;   /* once per instantiation: not legal inside a stream capture */ \
+      if (sh > 64 * 1024 && arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); } \
+      hipLaunchKernelGGL(kern, grid, dim3(256), sh, st, a);                                         \
+    } while (0)
+    if (co_b == 64 && ci_b == 64) WG(64, 64);
+    else if (co_b == 64 && ci_b == 32) WG(64, 32);
+    else if (co_b == 64 && ci_b == 16) WG(64, 16);
+    else if (co_b == 32 && ci_b == 64) WG(32, 64);
+    else if (co_b == 32 && ci_b == 32) WG(32, 32);
+    else if (co_b == 32 && ci_b == 16) WG(32, 16);
+    else if (co_b == 16 && ci_b == 64) WG(16, 64);
+    else if (co_b == 16 && ci_b == 32) WG(16, 32);
+    else WG(16, 16);
 #undef WG
+  }
+  arco_note_wgrad_route(p.route);
   launch_wgrad_reduce(st, ws, (int)chunks, taps, a.CoutPad, a.CinPad, Cout, Cin, dW, accumulate);
   return arco_launch_status();
 }
 
 // out[c] (+)= sum over pixels of X[pix][c];  ws holds 1024*C floats
 int arco_colsum(const float* X, long ldx, long M, int C, float* ws, float* out, int accumulate, void* stream) {
-  ARCO_CHECK_ARG(X && ws && out && M > 0 && C > 0);
+  ARCO_CHECK_ARG(X && ws && out && M > 0 && C > 0 && ldx >= C && (accumulate == 0 || accumulate == 1));
   int nblk = (int)((M + 511) / 512); if (nblk > 1024) nblk = 1024; if (nblk < 1) nblk = 1;
   hipLaunchKernelGGL(colsum_partial_kernel<float>, dim3(nblk), dim3(256), 1024 * sizeof(float), as_stream(stream), X, ldx, M, C, ws);
   hipLaunchKernelGGL(colsum_final_kernel, dim3(C), dim3(64), 0, as_stream(stream), ws, nblk, C, out, accumulate);
@@ -2518,7 +2636,7 @@ int arco_colsum(const float* X, long ldx, long M, int C, float* ws, float* out, 
 }
 // the same over an f16 tensor (f16 activation storage: bias gradients of the V-Net's convolutions)
 int arco_colsum_h(const void* X, long ldx, long M, int C, float* ws, float* out, int accumulate, void* stream) {
-  ARCO_CHECK_ARG(X && ws && out && M > 0 && C > 0);
+  ARCO_CHECK_ARG(X && ws && out && M > 0 && C > 0 && ldx >= C && (accumulate == 0 || accumulate == 1));
   int nblk = (int)((M + 511) / 512); if (nblk > 1024) nblk = 1024; if (nblk < 1) nblk = 1;
   hipLaunchKernelGGL(colsum_partial_kernel<_Float16>, dim3(nblk), dim3(256), 1024 * sizeof(float), as_stream(stream),
                      reinterpret_cast<const _Float16*>(X), ldx, M, C, ws);
@@ -2527,7 +2645,7 @@ int arco_colsum_h(const void* X, long ldx, long M, int C, float* ws, float* out,
 }
 
 int arco_transpose2d(const float* x, long ldx, int rows, int cols, float* y, long ldy, void* stream) {
-  ARCO_CHECK_ARG(rows > 0 && cols > 0);
+  ARCO_CHECK_ARG(x && y && rows > 0 && cols > 0 && ldx >= cols && ldy >= rows);
   hipLaunchKernelGGL(transpose2d_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(32, 8), 0, as_stream(stream),
                      x, ldx, rows, cols, y, ldy);
   return arco_launch_status();

@@ -301,16 +301,17 @@ int arco_conv3x3_image_fwd_h(const float* in, long ld_in, int K, const float* Wp
 // dW [16][K][3][3] (+)= sum_pix dZ (f16, 16 channels) x in (fp32 image); ws sized by arco_wgrad_ws_floats(16, K, 9, NB * H * W)
 int arco_conv3x3_image_wgrad_h(const void* dZ, long ld_dz, int Cout, const float* in, long ld_in, int K, int NB, int H, int W,
                                float* ws, float* dW, int accumulate, void* stream) {
-  ARCO_CHECK_ARG(dZ && in && ws && dW && K >= 1 && K <= 4 && ld_in >= K && NB > 0 && H > 0 && W > 0);
-  if (Cout != 16 || (ld_dz & 7) != 0 || (reinterpret_cast<uintptr_t>(dZ) & 15) != 0) return ARCO_ERR_UNSUPPORTED;
-  const long tiles = (long)NB * ((H + 15) / 16) * ((W + 15) / 16);
-  const long reserved = ((long)NB * H * W + 127) / 128 * 4 + 64;    // the slab count arco_wgrad_ws_floats reserves (<= 1536)
-  long chunks = tiles < 512 ? tiles : 512;
-  if (chunks > reserved) chunks = reserved;
+  ARCO_CHECK_ARG(dZ && in && ws && dW && K >= 1 && K <= 4 && ld_in >= K && NB > 0 && H > 0 && W > 0 && Cout > 0 && ld_dz >= Cout &&
+                 (accumulate == 0 || accumulate == 1));
+  arco_note_wgrad_route(0);
+  WgradPlan p;       // (the slab count never exceeds what arco_wgrad_ws_floats reserves: wgrad_plan clamps it)
+  const int rc = wgrad_plan(1, 9, NB, 1, H, W, K, Cout, ld_dz, ld_in, 4, false, 0, (reinterpret_cast<uintptr_t>(dZ) & 15) == 0, p);
+  if (rc != ARCO_OK) return rc;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(himage_wgrad_kernel, dim3((unsigned)chunks), dim3(256), 0, st, reinterpret_cast<const _Float16*>(dZ), ld_dz, in,
+  hipLaunchKernelGGL(himage_wgrad_kernel, dim3((unsigned)p.slabs), dim3(256), 0, st, reinterpret_cast<const _Float16*>(dZ), ld_dz, in,
                      ld_in, K, NB, H, W, ws);
-  launch_wgrad_reduce(st, ws, (int)chunks, 9, 16, 16, Cout, K, dW, accumulate);
+  arco_note_wgrad_route(p.route);
+  launch_wgrad_reduce(st, ws, (int)p.slabs, 9, p.CoutPad, p.CinPad, Cout, K, dW, accumulate);
   return arco_launch_status();
 }
 

@@ -191,6 +191,28 @@ int arco_conv3d_wgrad(const float* dZ, long ld_dz, int Cout, const float* in, lo
                       int D3, int H, int W, float* ws, float* dW, int accumulate,
                       int mma /* 0 exact fp32; != 0: 3x3x3 halo kernels with bf16 MFMA operands, fp32 accumulate */, void* stream);
 long arco_wgrad_ws_floats(int Cout, int Cin, int taps, long M);
+/* which weight-gradient kernel a launch uses, decided by the host function that the launch itself calls.  entry 0: arco_conv_wgrad /
+ * arco_conv3d_wgrad (pro_groups = 0) / arco_conv3d_wgrad_pro (pro_groups = its BatchNorm groups >= 1); entry 1:
+ * arco_conv3x3_image_wgrad_h (taps 9, D3 1, Cin = its K).  aligned16: dZ and `in` start on 16-byte boundaries.  Returns the id or
+ * ARCO_ERR_UNSUPPORTED (-3) where the launch would; *slabs = slabs written to ws (= workgroups along x, never more than
+ * arco_wgrad_ws_floats reserves for the same Cout, Cin, taps, M), *slab_floats = floats per slab, *reduce = the slab sum that follows:
+ * 1 wgrad_reduce_kernel<64,8>, 2 wgrad_reduce_kernel<16,32>, 3 wgrad_reduce4_kernel.  The three pointers may be NULL.
+ * mma 4 with Cin = 1 and taps >= 9 (f16 dZ against the fp32 one-channel volume) exists on wgrad_image3d_kernel only (Cout in 4, 8, 12,
+ * 16 and ld_dz a multiple of 4): any other such shape is ARCO_ERR_UNSUPPORTED, in the query and in the launch.
+ * Ids: T*1e6 + F*1e5 + V*1e4 + COB*100 + CIB, T = 1 (taps 1) or 9 (taps 9 and 27), COB x CIB the channel tile:
+ *   F 0  wgrad_kernel<COB,CIB>                  1001616 .. 1006464
+ *   F 1  wgrad_q_kernel<TP>                     1100064, 1100128 (TP in the CIB field)
+ *   F 2  wgrad_halo2_kernel<COB,CIB,FLAT,MODE>  V = FLAT + 2 * (bf16 operands): 9201616 rectangular fp32, 9211616 flat fp32, 9221616, 9231616
+ *   F 3  wgrad_split_kernel<COB,CIB,PRO>        V = PRO: 9301616 .. 9303232, 9311616 .. 9313232
+ *   F 4  wgrad_image3d_kernel<DEPTH>            V = DEPTH: 9411616, 9431616
+ *   F 5  hwgrad_kernel<COB/16,CIB/16,NT>        T = NT: 9501616 .. 9503232, 1501616 .. 1506464
+ *   F 6  himage_wgrad_kernel                    9601600 + K: 9601601 .. 9601604                                                    */
+int arco_wgrad_config(int entry, int taps, int NV, int D3, int H, int W, int Cin, int Cout, long ld_dz, long ld_in, int mma,
+                      int pro_groups, int aligned16, long* slabs, long* slab_floats, int* reduce);
+/* test-facing: the id, as above, of the kernel that the most recent weight-gradient launch on the calling thread took (arco_conv_wgrad,
+ * arco_conv3d_wgrad(_pro), arco_conv3x3_image_wgrad_h; the f16 kernels of mma 4 included).  0 before the first launch and after a call
+ * that found no kernel (ARCO_ERR_UNSUPPORTED); a call rejected with ARCO_ERR_ARG leaves it unchanged.  Host side only. */
+int arco_wgrad_last_route(void);
 
 /* ---- Consumer-side activation: a block's first Conv-BN-LeakyReLU-Dropout stage (unetWithArgs.py:36-44: conv_conv[0..3]) without the
  * BatchNorm-apply pass.  The producing convolution writes its PRE-activation z (and the BN partial statistics); the block's second

@@ -17,6 +17,9 @@ def test_library_exports_header_symbols():
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     assert "arco_conv_last_route" in declared          # the test-facing record of the kernel a forward launch took
     assert isinstance(_lib.query("arco_conv_last_route"), int)
+    assert {"arco_wgrad_config", "arco_wgrad_last_route"} <= declared      # ... and of the weight-gradient route, with its query
+    assert isinstance(_lib.query("arco_wgrad_last_route"), int)
+    assert _lib.query("arco_wgrad_config", 0, 9, 1, 1, 16, 16, 16, 16, 16, 16, 0, 0, 1, None, None, None) == 9201616
 
 
 def test_missing_library_fails_loudly(monkeypatch):
