@@ -148,6 +148,8 @@ _SIGS = {
     "arco_sgd_nesterov": [_P, _P, _P, _L, _F, _F, _F, _I, _P],
     "arco_sgd_momentum": [_P, _P, _P, _L, _F, _F, _F, _I, _P],
     "arco_ema": [_P, _P, _L, _F, _P],
+    "arco_ingest_slices": [_P, _P, _L, _P, _L, _P, _I, _I, _I, _P, _P, _P],
+    "arco_ingest_volumes": [_P, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P],
 }
 _QUERIES = {   # plain host helpers returning sizes
     "arco_proto_ws_floats": ([_L, _I, _I], _L),

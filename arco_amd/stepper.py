@@ -190,7 +190,8 @@ def paired_loaders(db_l, db_u, batch_size, generator=None):
 
 def train(args, snapshot_path, stepper_cls, synthetic, build_loaders):
     """The training loop of either rank: `stepper_cls` is ArcoStep2D / ArcoStep3D, `synthetic(b, patch, n_cls, seed, device)` makes
-    a synthetic (images, labels) batch, `build_loaders(args, generator=)` the two loaders of --synthetic 0."""
+    a synthetic (images, labels) batch, `build_loaders(args, generator=)` the two loaders of --synthetic 0 (--gpu_ingest 1 replaces
+    their datasets by device-resident banks and descriptor twins)."""
     rank, world = adist.init()
     if getattr(args, "dp_local_thresholds", 0):
         glue.state_reduce_hook = None
@@ -205,7 +206,15 @@ def train(args, snapshot_path, stepper_cls, synthetic, build_loaders):
             adist.seed_data_pipeline(args.seed)
     else:
         # data parallel: every rank draws its own samples / augmentations (seed + rank), after the weight broadcast above
-        loaders = build_loaders(args, generator=adist.seed_data_pipeline(args.seed) if world > 1 else None)
+        generator = adist.seed_data_pipeline(args.seed) if world > 1 else None
+        loaders = build_loaders(args, generator=generator)
+        if getattr(args, "gpu_ingest", 0):
+            # the datasets go to device memory once (one bank per stream, per rank); from here on a batch is a handful of drawn
+            # parameters per sample and one kernel launch, equal to the host loaders' batch bit for bit (dataloaders/gpu_ingest.py)
+            from .dataloaders import gpu_ingest
+            loaders = gpu_ingest.bank_loaders(loaders, paired_loaders, b, dev, generator)
+            logging.info("gpu ingest: {} + {} cases, {:.1f} MB of device memory".format(
+                loaders[0].bank.n_cases, loaders[1].bank.n_cases, (loaders[0].bank.nbytes + loaders[1].bank.nbytes) / 1e6))
         iters_per_epoch = len(loaders[1])                              # 2-D :217 iterations per epoch = unlabeled batches
         logging.info("{} iterations per epoch".format(iters_per_epoch))
         resume = "../model/{}_{}_labeledfinal/{}/iter_30000.pth".format(args.resume, args.labeled_num, args.model)

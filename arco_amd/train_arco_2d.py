@@ -85,6 +85,10 @@ def build_parser():
     # additions of this implementation (not in the reference)
     p.add_argument('--queue_size', type=int, default=0, help='override per-class bank size (0 = reference 50000/30000)')
     p.add_argument('--synthetic', type=int, default=0, help='1: train on synthetic ACDC-shaped tensors')
+    p.add_argument('--gpu_ingest', type=int, default=0, choices=[0, 1],
+                   help='1 (with --synthetic 0): hold both datasets in device memory and build every batch with one HIP launch from the '
+                        'transform parameters drawn on the host - the same draws, the same batches bit for bit, no scipy per sample '
+                        '(dataloaders/gpu_ingest.py); 0: the host loaders')
     p.add_argument('--in_chns', type=int, default=1, help='input channels (reference: 1)')
     p.add_argument('--graphs', type=int, default=1, help='1: replay the no-grad U-Net forwards as HIP graphs')
     p.add_argument('--batched_passes', type=int, default=1,

@@ -581,6 +581,16 @@ int arco_maxpool2_bwd_add_h(const void* X, long ldx, int NB, int H, int W, int C
                             long ld_add, void* dX, long ldo, void* stream);
 int arco_bilinear_fwd_h(const void* X, long ldx, int NB, int Hi, int Wi, int C, int Ho, int Wo, void* Y, long ldy, void* stream);
 int arco_bilinear_bwd_h(const void* dY, long ldy, int NB, int Hi, int Wi, int C, int Ho, int Wo, void* dX, long ldx, void* stream);
+/* Data ingest from a GPU-resident dataset (trainers' --gpu_ingest 1; csrc/ingest.hip, arco_amd/dataloaders/gpu_ingest.py): one launch
+ * per batch reproduces the host transforms bit for bit - 2-D: zoom(order=0) to the patch, then none / rot90 + flip / rotate(order=0) /
+ * centre crop; 3-D: RandomRotFlip -> RandomCrop -> ToTensor.  bank_img / bank_lab: the packed cases (fp32 / uint8, bank_elems elements
+ * each); table: [n_cases][4] int64 {offset, n0, n1, n2}; desc, on the device: 2-D [B][16] float64 {case, op, Z0, Z1, z0, z1, a, b, m00, m01,
+ * m10, m11, off0, off1, -, -}, 3-D [B][8] int64 {case, k, axis, s0, s1, s2, -, -}.  out_img [B,1,...] fp32, out_lab [B,...] int64 or null;
+ * the fastest output axis a multiple of 4.  Coordinates in float64 without contraction (scipy.ndimage's order-0 rule). */
+int arco_ingest_slices(const float* bank_img, const unsigned char* bank_lab, long bank_elems, const long* table, long n_cases,
+                       const double* desc, int B, int H, int W, float* out_img, long* out_lab, void* stream);
+int arco_ingest_volumes(const float* bank_img, const unsigned char* bank_lab, long bank_elems, const long* table, long n_cases,
+                        const long* desc, int B, int X, int Y, int Z, float* out_img, long* out_lab, void* stream);
 
 #ifdef __cplusplus
 }
