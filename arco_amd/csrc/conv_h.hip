@@ -331,14 +331,15 @@ static long h_rect_blocks(const IgemmArgs& a, int bm, int bn) {
 static long h_flat_blocks(const IgemmArgs& a, int bm, int bn) {
   return (long)a.NB * ((a.H * (a.W + 2) + bm - 1) / bm) * ((a.Npad + bn - 1) / bn);
 }
+constexpr long HCONV_WANT_BLOCKS = 256;      // one workgroup per CU
 template <bool FLAT>
 static int hconv_dispatch3(const IgemmArgs& a, hipStream_t st, int* q) {
-  static const long want = getenv("ARCO_HCONV_WANT") ? atol(getenv("ARCO_HCONV_WANT")) : 256;      // (the deep levels run better on the larger tiles even with one workgroup per CU: 128 ch 39.8 -> 37.6 us)
+  constexpr long want = HCONV_WANT_BLOCKS;      // (the deep levels run better on the larger tiles even with one workgroup per CU: 128 ch 39.8 -> 37.6 us)
   auto blocks = [&](int bm, int bn) { return FLAT ? h_flat_blocks(a, bm, bn) : h_rect_blocks(a, bm, bn); };
   if (a.Npad <= 16) return launch_hconv<9, 128, 16, 4, 1, 3, FLAT>(a, st, q);
   if (a.Npad <= 32) {
-    static const int big = getenv("ARCO_HCONV_256") ? atoi(getenv("ARCO_HCONV_256")) : 1;      // 256-pixel tiles (4 x 2 MFMA tiles per wave: 6 fragment reads per 8 MFMAs instead of 4 per 4): 32 -> 32 @80x80x48 x2 63 -> 54 us; 0 = off
-    if (big && !FLAT && blocks(256, 32) >= want) return launch_hconv<9, 256, 32, 4, 1, 3, false>(a, st, q);
+    // 256-pixel tiles (4 x 2 MFMA tiles per wave: 6 fragment reads per 8 MFMAs instead of 4 per 4): 32 -> 32 @80x80x48 x2 63 -> 54 us
+    if (!FLAT && blocks(256, 32) >= want) return launch_hconv<9, 256, 32, 4, 1, 3, false>(a, st, q);
     if (blocks(128, 32) >= want) return launch_hconv<9, 128, 32, 4, 1, 3, FLAT>(a, st, q);
     return launch_hconv<9, 64, 32, 2, 2, 3, FLAT>(a, st, q);
   }
@@ -350,8 +351,8 @@ static int hconv_dispatch3(const IgemmArgs& a, hipStream_t st, int* q) {
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Resident-weights form for the shallow levels (3x3x3, K = N = 16 on 8 x 16 tiles / 256 threads, K = N = 32 on 16 x 16 tiles / 512
-// threads; planes with H % TH == 0 and W % 16 == 0: the V-Net's 160x160x96 / 80x80x48 levels).  hconv_kernel re-stages a tile's weights (27 taps: as many bytes as the activations at these
+// Resident-weights form for the shallow levels (3x3x3, K = N = 16 on 8 x 16 tiles / 256 threads - the only instantiation built; K = N = 32 on
+// 16 x 16 tiles / 512 threads was retired; planes with H % TH == 0 and W % 16 == 0: the V-Net's 160x160x96 / 80x80x48 levels).  hconv_kernel re-stages a tile's weights (27 taps: as many bytes as the activations at these
 // widths) and reads every input plane three times; here a persistent workgroup
 //   * copies ALL 27 taps' weights to LDS once per launch,
 //   * owns units of (volume, TH x 16 tile, S consecutive planes) and walks the depth axis with a RING of three input plane
@@ -539,10 +540,9 @@ static int hconv_cus() {
   return n;
 }
 static bool hconv_rw_eligible(const IgemmArgs& a) {
-  static const int mode = getenv("ARCO_HCONV_RW") ? atoi(getenv("ARCO_HCONV_RW")) : 1;      // A/B switch: bit 0: 16 channels (default), bit 1: 32 (16 x 16 tiles, 512 threads: measured level with hconv_kernel, 502 vs 521 TFLOP/s in the step - off)
-  const bool on = a.K == 16 ? (mode & 1) : (mode & 2);
-  const int th = a.K == 16 ? ((mode & 4) && a.H % 16 == 0 ? 16 : 8) : 16;
-  return on && a.K == a.N && (a.K == 16 || a.K == 32) && a.Npad == a.N && a.H % th == 0 && (a.W & 15) == 0 && (a.lda & 7) == 0 &&
+  // 16 channels on 8 x 16 tiles only (the 32-channel form on 16 x 16 tiles measured level with hconv_kernel, 502 vs 521 TFLOP/s in
+  // the step, and was retired with the 16 x 16 tiles at 16 channels)
+  return a.K == 16 && a.N == 16 && a.Npad == a.N && a.H % 8 == 0 && (a.W & 15) == 0 && (a.lda & 7) == 0 &&
          (a.ldc & 3) == 0 && a.R == nullptr && a.Kpad == 32;
 }
 // BN slabs: one per plane tile, NB * (H / TH) * (W / 16) (a function of the plane count alone, like the other kernels' counts)
@@ -839,12 +839,10 @@ static int launch_hfc(const IgemmArgs& a, hipStream_t st, int* q) {
   return arco_launch_status();
 }
 
-// -1: shape not taken.  A/B: ARCO_HCONV_FC=0 off; ARCO_HCONV_FC_CFG=<A_T><C_T> forces a tile shape.  arco_conv3d_fl_set(0) switches it off too.
+// -1: shape not taken.  ARCO_HCONV_FC_CFG=<A_T><C_T> forces a tile shape (tests); arco_conv3d_fl_set(0) switches the form off.
 extern "C" int arco_conv3d_fl_set(int on);
 static int hconv_fc_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
-  static const int on = getenv("ARCO_HCONV_FC") ? atoi(getenv("ARCO_HCONV_FC")) : 1;
   static const int forced = getenv("ARCO_HCONV_FC_CFG") ? atoi(getenv("ARCO_HCONV_FC_CFG")) : 0;
-  if (!on) return -1;
   { const int cur = arco_conv3d_fl_set(1); if (!cur) { arco_conv3d_fl_set(0); return -1; } }
   if ((a.K & 15) != 0 || a.K < 16 || (a.N & 31) != 0 || a.N != a.Npad || a.N > 256 || a.W + 2 > 63 || (a.lda & 7) != 0 || (a.ldc & 3) != 0) return -1;
   if ((long)a.H * a.W * a.lda >= (1l << 30)) return -1;
@@ -859,11 +857,10 @@ static int hconv_fc_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
     // one), or the MFMA / rendezvous path if that is longer, + 1.9 us of epilogue per round
     double bc = 1e300;
     // (A_T = 5 / 6 with 64-wide blocks, round 6: a chunk's 20 KB of weights serve 320 / 384 positions - the stream per position drops
-    //  from 148 to 90 B at 40 x 24 planes; ARCO_HCONV_FC_BIG=0 leaves them out)
-    static const int big = getenv("ARCO_HCONV_FC_BIG") ? atoi(getenv("ARCO_HCONV_FC_BIG")) : 1;
-    const int cand[10] = {64, 54, 44, 34, 24, 14, 42, 32, 22, 12};      // (<6,2> / <5,2> exist for ARCO_HCONV_FC_CFG only: 58-69 us against hconv_kernel's 53 at 80 x 80 x 48)
+    //  from 148 to 90 B at 40 x 24 planes)
+    const int cand[10] = {64, 54, 44, 34, 24, 14, 42, 32, 22, 12};      // (<6,2> / <5,2> ran 58-69 us against hconv_kernel's 53 at 80 x 80 x 48 and were retired)
     const int cus = conv_sp_cus();
-    for (int i = big ? 0 : 2; i < 10; ++i) {
+    for (int i = 0; i < 10; ++i) {
       const int a_t = cand[i] / 10, c_t = cand[i] % 10;
       if ((a.N % (16 * c_t)) != 0) continue;
       const long tiles = (long)a.NB * ((a.H * (a.W + 2) + 64 * a_t - 1) / (64 * a_t)) * (a.Npad / (16 * c_t));
@@ -884,8 +881,6 @@ static int hconv_fc_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
     case 34: if ((a.N & 63) == 0) return launch_hfc<3, 4>(a, st, q); break;
     case 24: if ((a.N & 63) == 0) return launch_hfc<2, 4>(a, st, q); break;
     case 14: if ((a.N & 63) == 0) return launch_hfc<1, 4>(a, st, q); break;
-    case 62: return launch_hfc<6, 2>(a, st, q);
-    case 52: return launch_hfc<5, 2>(a, st, q);
     case 42: return launch_hfc<4, 2>(a, st, q);
     case 32: return launch_hfc<3, 2>(a, st, q);
     case 22: return launch_hfc<2, 2>(a, st, q);
@@ -961,8 +956,7 @@ __global__ __launch_bounds__(256) void hconv1x1_narrow_in_kernel(IgemmArgs a) {
   }
 }
 static int hconv1x1_stream_dispatch(const IgemmArgs& a, hipStream_t st) {
-  static const int on = getenv("ARCO_CONV1X1_STREAM") ? atoi(getenv("ARCO_CONV1X1_STREAM")) : 1;
-  if (!on || a.stat_sum || a.R || a.pro.mean || a.Rup || a.ksplit > 1 || a.batch > 1 || a.M < 65536) return -1;
+  if (a.stat_sum || a.R || a.pro.mean || a.Rup || a.ksplit > 1 || a.batch > 1 || a.M < 65536) return -1;
   long blocks;
   if (a.N >= 1 && a.N <= 4 && (a.K == 8 || a.K == 16 || a.K == 32) && (a.lda & 7) == 0 && (reinterpret_cast<uintptr_t>(a.A) & 15) == 0) {
     const int Q = a.K / 8;
@@ -985,7 +979,7 @@ static int hconv1x1_stream_dispatch(const IgemmArgs& a, hipStream_t st) {
 // 3x3 on 2-D maps (the U-Net): hconv_kernel's plane step without the depth loop (DEPTH = 1), rectangular tiles of BM / 16 rows x 16
 // columns (ragged at the edges).  Tile choice as hconv_dispatch3's: the largest tile that still gives `want` workgroups.
 static int hconv_dispatch2(const IgemmArgs& a, hipStream_t st, int* q) {
-  static const long want = getenv("ARCO_HCONV2_WANT") ? atol(getenv("ARCO_HCONV2_WANT")) : 256;
+  constexpr long want = HCONV_WANT_BLOCKS;
   auto blocks = [&](int bm, int bn) { return h_rect_blocks(a, bm, bn); };
   if (a.Npad <= 16) return blocks(128, 16) >= want ? launch_hconv<9, 128, 16, 4, 1, 1, false>(a, st, q) : launch_hconv<9, 64, 16, 4, 1, 1, false>(a, st, q);
   if (a.Npad <= 32) {
@@ -1008,11 +1002,7 @@ int hconv_dispatch(const IgemmArgs& a, int taps, hipStream_t st, int* q) {
   }
   if (!q && (((reinterpret_cast<uintptr_t>(a.A) & 15) != 0 && (a.K & 7) == 0) || (reinterpret_cast<uintptr_t>(a.Wp) & 15) != 0)) return ARCO_ERR_ARG;
   if (taps == 27) {
-    if (hconv_rw_eligible(a)) {
-      static const int mode = getenv("ARCO_HCONV_RW") ? atoi(getenv("ARCO_HCONV_RW")) : 1;
-      if (a.K == 16) return ((mode & 4) && a.H % 16 == 0) ? launch_hconv_rw<1, 1, 16>(a, st, q) : launch_hconv_rw<1, 1, 8>(a, st, q);
-      return launch_hconv_rw<2, 2, 16>(a, st, q);
-    }
+    if (hconv_rw_eligible(a)) return launch_hconv_rw<1, 1, 8>(a, st, q);
     { const int r = hconv_fc_dispatch(a, st, q); if (r != -1) return r; }      // the pipelined flat-tile form (32 .. 256 channels)
     if ((a.W & 15) != 0 && a.W + 2 <= HFLAT_WPMAX) return hconv_dispatch3<true>(a, st, q);
     return hconv_dispatch3<false>(a, st, q);

@@ -520,7 +520,7 @@ __global__ __launch_bounds__((NCW + 4) * 64) void conv3x3_rw_kernel(IgemmArgs a)
       // WAVE-UNIFORM choice (every wave must issue exactly NA load instructions: the vmcnt waits count them)
       const bool border = !real || d.y0 == 0 || d.y0 + TH == a.H || d.x0 == 0 || d.x0 + 16 == a.W || d.c * 16 + 16 > a.K;
       if constexpr (PRO) bord2[set] = border;
-#ifdef RW_NO_LOAD          // (timing-only ablation builds, tools/debug/rw_abl.sh: never in the shipped library)
+#ifdef RW_NO_LOAD          // (timing-only ablation builds with -DRW_NO_...: never in the shipped library)
       if (true) { (void)gbase; } else
 #endif
       if (!border) {
@@ -742,7 +742,7 @@ __global__ __launch_bounds__((NCW + 4) * 64) void conv3x3_rw_kernel(IgemmArgs a)
   }
 }
 
-template <int A_T, int C_T, int NCW = 4>
+template <int A_T, int C_T, int NCW>
 static int launch_rw(const IgemmArgs& a, hipStream_t st, int* q) {
   using G = RwGeom<A_T, C_T, NCW>;
   const int mblocks = a.NB * (a.H / G::TH) * (a.W / 16);
@@ -954,8 +954,7 @@ __global__ __launch_bounds__(512) void conv3d_rw16_kernel(IgemmArgs a, int S, in
 
 // returns -1 when the shape is not taken (the caller falls through to igemm_kernel)
 int conv3d_rw_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
-  static const bool off = getenv("ARCO_CONV3D_RW") && atoi(getenv("ARCO_CONV3D_RW")) == 0;      // A/B switch
-  if (off || a.mma != 3 || a.K != 16 || a.N != 16 || a.Npad != 16 || a.Kg != 2 || (a.H & 15) != 0 || (a.W & 15) != 0 ||
+  if (a.mma != 3 || a.K != 16 || a.N != 16 || a.Npad != 16 || a.Kg != 2 || (a.H & 15) != 0 || (a.W & 15) != 0 ||
       (a.lda & 3) != 0 || (a.ldc & 3) != 0 || a.R != nullptr) return -1;
   using G = Rw3Geom;
   const long tiles = (long)(a.H / G::TH) * (a.W >> 4);
@@ -976,8 +975,8 @@ int conv3d_rw_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
   return arco_launch_status();
 }
 
-// A/B knob: ARCO_CONV_SP=0 / arco_conv_sp_set(0) keeps every shape on igemm_kernel
-static int& conv_sp_flag() { static int on = !(getenv("ARCO_CONV_SP") && atoi(getenv("ARCO_CONV_SP")) == 0); return on; }
+// arco_conv_sp_set(0) keeps every shape on igemm_kernel
+static int& conv_sp_flag() { static int on = 1; return on; }
 static bool conv_sp_on() { return conv_sp_flag() != 0; }
 extern "C" int arco_conv_sp_set(int on) { const int prev = conv_sp_flag(); conv_sp_flag() = on ? 1 : 0; return prev; }
 
@@ -992,32 +991,25 @@ static int dispatch_rows(const IgemmArgs& a, hipStream_t st, int* q, int min_til
   return -1;
 }
 
+constexpr int CONV_SP_MIN_TILES = 192;      // work items a launch must have: decides the tile height, and below it the shape stays on igemm_kernel
 int conv_sp_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
   if (!conv_sp_on() || a.mma != 3 || a.D3 != 1) return -1;
   if ((a.lda & 3) != 0 || (a.W & 15) != 0 || (a.H & 3) != 0) return -1;
-  static const int min_tiles = getenv("ARCO_CONV_SP_TILES") ? atoi(getenv("ARCO_CONV_SP_TILES")) : 192;
-  static const int min_n = getenv("ARCO_CONV_SP_MINN") ? atoi(getenv("ARCO_CONV_SP_MINN")) : 16;
-  static const int rw = getenv("ARCO_CONV_RW") ? atoi(getenv("ARCO_CONV_RW")) : 1;
-  static const int narrow = getenv("ARCO_CONV_RW_NARROW") ? atoi(getenv("ARCO_CONV_RW_NARROW")) : 1;
+  constexpr int min_tiles = CONV_SP_MIN_TILES;
   // one 16-wide output block from at most 32 inputs: also the few-channel ends of the network (the 16 -> 4 logits layer, its
   // 4 -> 16 data gradient) - HBM-bound launches, the idle MFMA columns / zero channels cost nothing
-  if (rw && a.Npad == 16 && (a.N & 3) == 0 && (a.N == 16 || narrow) && a.K <= 32 && (a.K & 3) == 0 && ((a.K & 15) == 0 || (a.K < 16 && narrow)) &&
+  if (a.Npad == 16 && (a.N & 3) == 0 && a.K <= 32 && (a.K & 3) == 0 && ((a.K & 15) == 0 || a.K < 16) &&
       (a.H & 31) == 0 && (long)a.NB * (a.H / 32) * (a.W / 16) >= min_tiles) {
     // eight MFMA waves (two per SIMD) on the same 32 x 16 tiles (round 6): a one-chunk tile (K <= 16) is 240 MFMAs against an epilogue of the same
     // order, and the second wave's MFMAs run under it - tools/micro/rw_bench.py (inputs from HBM): 52.5 -> 49.2 us at 16 -> 16 @256^2 x16, 47.3 -> 43.7 at
     // 16 -> 4, 40.7 -> 38.2 at 4 -> 16, 40.2 -> 38.9 at 32 -> 32 @128^2 (<2,2,8>), 81 -> 82-87 at 32 -> 16 (two chunks per tile).  In bench.py's event-timed
     // pass the family averages 43.4 us with four waves, 41.7 with eight at K <= 16, 40.3 with eight everywhere (roofline.frac 0.313 / 0.327 / 0.340);
-    // the replayed step 10.57 / 10.48 / 10.52 ms (five alternations, one box).  ARCO_CONV_RW8 = 0: four waves, 1: eight at K <= 16, 2 (default): eight
-    static const int rw8 = getenv("ARCO_CONV_RW8") ? atoi(getenv("ARCO_CONV_RW8")) : 2;
-    if (rw8 == 2 || (rw8 == 1 && a.K <= 16)) return launch_rw<4, 1, 8>(a, st, q);
-    return launch_rw<8, 1>(a, st, q);
+    // the replayed step 10.57 / 10.48 / 10.52 ms (five alternations, one box): eight waves everywhere; the four-wave forms <8,1> and <4,2> were retired
+    return launch_rw<4, 1, 8>(a, st, q);
   }
   if ((a.K & 15) != 0 || a.K < 16 || (a.N & 15) != 0 || a.N != a.Npad || a.N > 256) return -1;
-  if (a.N < min_n) return -1;
-  if (rw && a.K <= 32 && a.N == 32) {                           // shallow levels: resident weights, one rendezvous per chunk
-    static const int rw8b = getenv("ARCO_CONV_RW8") ? atoi(getenv("ARCO_CONV_RW8")) : 2;
-    if ((a.H & 15) == 0 && (long)a.NB * (a.H / 16) * (a.W / 16) >= min_tiles) return rw8b == 2 ? launch_rw<2, 2, 8>(a, st, q) : launch_rw<4, 2>(a, st, q);
-  }
+  if (a.K <= 32 && a.N == 32 && (a.H & 15) == 0 && (long)a.NB * (a.H / 16) * (a.W / 16) >= min_tiles)
+    return launch_rw<2, 2, 8>(a, st, q);                        // shallow levels: resident weights, one rendezvous per chunk
   if ((a.N & 63) == 0) return dispatch_rows<4>(a, st, q, min_tiles);
   if ((a.N & 31) == 0) return dispatch_rows<2>(a, st, q, min_tiles);
   return (a.H & 15) == 0 ? launch_sp<4, 1>(a, st, q) : -1;

@@ -384,8 +384,8 @@ __global__ __launch_bounds__(512) void gemm_sp_kernel(IgemmArgs a) {
 }
 
 // -1: the shape is not taken (the caller falls through to igemm_kernel); q != nullptr: query only
-static int& gemm_sp_flag() { static int on = !(getenv("ARCO_GEMM_SP") && atoi(getenv("ARCO_GEMM_SP")) == 0); return on; }
-static long& gemm_sp_min_tiles() { static long t = getenv("ARCO_GEMM_SP_TILES") ? atol(getenv("ARCO_GEMM_SP_TILES")) : 2048; return t; }
+static int& gemm_sp_flag() { static int on = 1; return on; }
+static long& gemm_sp_min_tiles() { static long t = 2048; return t; }
 // A/B switch (tests, tools): on = 0 keeps every GEMM on igemm_kernel; min_tiles > 0 also sets the tile-count threshold.  Returns the previous `on`.
 extern "C" int arco_gemm_sp_set(int on, long min_tiles) {
   const int prev = gemm_sp_flag();

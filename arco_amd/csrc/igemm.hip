@@ -519,17 +519,11 @@ static long conv_blocks(const IgemmArgs& a, int bm, int bn) {
 static long flat_blocks(const IgemmArgs& a, int bm, int bn) {
   return (long)a.NB * ((a.H * (a.W + 2) + bm - 1) / bm) * ((a.Npad + bn - 1) / bn);
 }
-static long want_blocks(const IgemmArgs& a) {      // A/B knob: ARCO_IGEMM_WANT / ARCO_IGEMM_WANT3 (split-bf16 launches)
-  static const long w0 = getenv("ARCO_IGEMM_WANT") ? atol(getenv("ARCO_IGEMM_WANT")) : 512;
-  static const long w3 = getenv("ARCO_IGEMM_WANT3") ? atol(getenv("ARCO_IGEMM_WANT3")) : 512;
-  return a.mma == 3 ? w3 : w0;
-}
+constexpr long IGEMM_WANT_BLOCKS = 512;      // 2 workgroups per CU, for every operand mode
 static int dispatch_flat3(const IgemmArgs& a, hipStream_t st, int* nmb) {
-  const long want = want_blocks(a);
+  constexpr long want = IGEMM_WANT_BLOCKS;
   if (a.Npad <= 16) return launch_igemm<9, 128, 16, 4, 1, 16, false, 3, true>(a, st, nmb);
   if (a.Npad <= 32) {
-    static const int big = getenv("ARCO_IGEMM_256") ? atoi(getenv("ARCO_IGEMM_256")) : 0;      // A/B: 256-position tiles (4 x 2 MFMA tiles per wave)
-    if (big && a.mma == 3 && flat_blocks(a, 256, 32) >= want) return launch_igemm<9, 256, 32, 4, 1, 16, false, 3, true>(a, st, nmb);
     if (flat_blocks(a, 128, 32) >= want) return launch_igemm<9, 128, 32, 4, 1, 16, false, 3, true>(a, st, nmb);
     return launch_igemm<9, 64, 32, 2, 2, 16, false, 3, true>(a, st, nmb);
   }
@@ -540,7 +534,7 @@ static int dispatch_flat3(const IgemmArgs& a, hipStream_t st, int* nmb) {
 }
 template <int DEPTH>
 static int dispatch_spatial(const IgemmArgs& a, hipStream_t st, int* nmb) {
-  const long want = want_blocks(a);
+  constexpr long want = IGEMM_WANT_BLOCKS;
   if (DEPTH == 3 && (a.W & 15) != 0 && a.W + 2 <= IGEMM_FLAT_WPMAX) return dispatch_flat3(a, st, nmb);
   if (a.Npad <= 16) {
     if (DEPTH == 1 && conv_blocks(a, 256, 16) >= want) return launch_igemm<9, 256, 16, 4, 1, 16, false, DEPTH>(a, st, nmb);
@@ -709,8 +703,6 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(IgemmArgs a) {
 
 // eligibility + launch; the block count (= BN-stat slabs per channel) is a pure function of the geometry
 static bool halo_eligible(const IgemmArgs& a) {
-  static const bool off = getenv("ARCO_CONV_HALO") && atoi(getenv("ARCO_CONV_HALO")) == 0;   // A/B switch
-  if (off) return false;
   return (a.K == 16 || a.K == 32) && a.Kpad == a.K && a.Npad <= 32 && (a.N & 3) == 0 && (a.lda & 3) == 0;
 }
 template <int CIN, int COUT, int TW>
@@ -988,10 +980,9 @@ __global__ __launch_bounds__(256) void conv1x1_narrow_in_kernel(IgemmArgs a) {
     *reinterpret_cast<f32x4*>(a.C + row * a.ldc + 4 * lq) = y;
   }
 }
-// -1: not taken.  ARCO_CONV1X1_STREAM=0: off (A/B)
+// -1: not taken
 static int conv1x1_stream_dispatch(const IgemmArgs& a, hipStream_t st) {
-  static const int on = getenv("ARCO_CONV1X1_STREAM") ? atoi(getenv("ARCO_CONV1X1_STREAM")) : 1;
-  if (!on || a.stat_sum || a.pro.mean || a.Rup || a.ksplit > 1 || a.batch > 1 || a.M < 65536 || (a.mma != 3 && a.mma != 0)) return -1;
+  if (a.stat_sum || a.pro.mean || a.Rup || a.ksplit > 1 || a.batch > 1 || a.M < 65536 || (a.mma != 3 && a.mma != 0)) return -1;
   const long rows_per_block_min = 8;
   if (!a.R && a.N >= 1 && a.N <= 4 && (a.K == 4 || a.K == 8 || a.K == 16 || a.K == 32) && (a.lda & 3) == 0 &&
       (reinterpret_cast<uintptr_t>(a.A) & 15) == 0) {
@@ -1036,11 +1027,7 @@ static int dispatch_igemm(const IgemmArgs& a, int taps, hipStream_t st, int* nmb
     }
     if ((a.Npad + 223) / 224 * 224 < (a.Npad + 127) / 128 * 128) {
       // N = 448 / 192 / 224 ...: 224-wide tiles pad N least, but the 64 x 224 split tile is single-buffered (50 KB of B
-      // planes per chunk); A/B knob ARCO_GEMM224: 0 = 64 x 224 (round 2), 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 128
-      static const int g224 = getenv("ARCO_GEMM224") ? atoi(getenv("ARCO_GEMM224")) : 0;
-      if (g224 == 1 && (a.Npad & 63) == 0) return launch_igemm<1, 64, 64, 2, 2, 32, true>(a, st, nmb);
-      if (g224 == 2 && (a.Npad & 63) == 0) return launch_igemm<1, 128, 64, 2, 2, 32, true>(a, st, nmb);
-      if (g224 == 3) return launch_igemm<1, 128, 128, 2, 2, 32, true>(a, st, nmb);
+      // planes per chunk); 64 x 64, 128 x 64 and 128 x 128 tiles were tried in its place and did not win
       return launch_igemm<1, 64, 224, 2, 2, 32, false>(a, st, nmb);
     }
     return launch_igemm<1, 128, 128, 2, 2, 32, true>(a, st, nmb);
@@ -1359,7 +1346,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
 // travelling global -> registers under the current tile's 512 fp32 MFMAs per wave.  Same products and per-block summation
 // order over pixels as wgrad_kernel within a slab; slabs are summed in fixed order by wgrad_reduce_kernel.
 // ---------------------------------------------------------------------------
-template <int TP>       // pixels per staged tile: 128 (139 KB of LDS, one workgroup per CU) or 64 (70 KB, two per CU)
+template <int TP>       // pixels per staged tile: 64 (70 KB of LDS, two workgroups per CU; 128 needed 139 KB, one per CU, and was retired)
 __global__ __launch_bounds__(256) void wgrad_q_kernel(WgradArgs a) {
   constexpr int CO_B = 128, CI_B = 128, LDZ = CO_B + WGRAD1_PAD, LDA = CI_B + WGRAD1_PAD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1960,8 +1947,7 @@ __global__ __launch_bounds__(512) void wgrad_reduce4_kernel(const float* __restr
 // which slab reduction follows a launch of `chunks` slabs: 1 wgrad_reduce_kernel<64,8>, 2 wgrad_reduce_kernel<16,32>, 3 wgrad_reduce4_kernel
 int wgrad_reduce_kind(long chunks, int taps, int CinPad, int Cout, int Cin) {
   const long tot = (long)Cout * Cin * taps;
-  static const bool v4 = !(getenv("ARCO_WGRAD_REDUCE4") && atoi(getenv("ARCO_WGRAD_REDUCE4")) == 0);
-  if (v4 && chunks > 16 && (Cin & 3) == 0 && (CinPad & 3) == 0 && tot >= 64 * 64) return 3;
+  if (chunks > 16 && (Cin & 3) == 0 && (CinPad & 3) == 0 && tot >= 64 * 64) return 3;
   return chunks > 16 ? 2 : 1;
 }
 void launch_wgrad_reduce(hipStream_t st, const float* ws, int chunks, int taps, int CoutPad, int CinPad, int Cout, int Cin,
@@ -2134,11 +2120,10 @@ int arco_conv_split_ok(int taps, int NB, int H, int W, int Cin, int Cout, long l
     if (image_conv3d_eligible(a)) return 0;
     if (image_conv_eligible(a) || (halo_eligible(a) && a.K == 16 && a.Npad <= 16)) {
       // ... unless the resident-weights pipelined kernel takes the launch (16 x 256^2 planes: HBM-bound there, the halo
-      // kernel is not); A/B switch ARCO_CONV_RW16=0
-      static const bool rw16 = !(getenv("ARCO_CONV_RW16") && atoi(getenv("ARCO_CONV_RW16")) == 0);
+      // kernel is not)
       int q[3];
       a.mma = 3;
-      return rw16 && conv_sp_dispatch(a, nullptr, q) == ARCO_OK && q[1] == 9358016 ? 1 : 0;     // (conv3x3_rw_kernel<8,1> only)
+      return conv_sp_dispatch(a, nullptr, q) == ARCO_OK && q[1] == 9358016 ? 1 : 0;     // (the 32 x 16-pixel tile of conv3x3_rw_kernel<4,1,.,8> only)
     }
     return 1;
   }
@@ -2356,6 +2341,7 @@ int arco_conv_wgrad(const float* dZ, long ld_dz, int Cout, const float* in, long
 }  // extern "C"
 
 // ---- the weight-gradient route: kernel, tile, flat or rectangular, slab count and reduction, in pure host code ------------------------
+constexpr long WGRAD_TARGET_BLOCKS = 512;      // two resident workgroups per CU, several tiles each
 static int wgrad_plan_finish(WgradPlan& p, int tapform, int fam, int var, int cob, int cib, long slabs, int taps, int Cout, int Cin, long M) {
   p.family = fam; p.cob = cob; p.cib = cib;
   p.slab_floats = (long)taps * p.CoutPad * p.CinPad;
@@ -2397,16 +2383,14 @@ int wgrad_plan(int entry, int taps, int NV, int D3, int H, int W, int Cin, int C
       p.CoutPad = (Cout + hco - 1) / hco * hco; p.CinPad = (Cin + hci - 1) / hci * hci;
       p.n_tiles = NB * ((H + 7) / 8) * ((W + 15) / 16);
       p.zdim = taps / 9; p.ydim = (p.CoutPad / hco) * (p.CinPad / hci);
-      static const long target = getenv("ARCO_HWGRAD_TARGET") ? atol(getenv("ARCO_HWGRAD_TARGET")) : 512;
-      long chunks = target / ((long)p.zdim * p.ydim); if (chunks > p.n_tiles) chunks = p.n_tiles;
+      long chunks = WGRAD_TARGET_BLOCKS / ((long)p.zdim * p.ydim); if (chunks > p.n_tiles) chunks = p.n_tiles;
       return wgrad_plan_finish(p, 9, WG_F_HGRAD, 0, hco, hci, chunks, taps, Cout, Cin, M);
     }
     const int co_b = Cout >= 64 ? 64 : (Cout > 16 ? 32 : 16), ci_b = Cin >= 64 ? 64 : (Cin > 16 ? 32 : 16);
     p.CoutPad = (Cout + co_b - 1) / co_b * co_b; p.CinPad = (Cin + ci_b - 1) / ci_b * ci_b;
     p.n_tiles = (int)((M + 127) / 128);
     p.ydim = (p.CoutPad / co_b) * (p.CinPad / ci_b);
-    static const long target1 = getenv("ARCO_HWGRAD1_TARGET") ? atol(getenv("ARCO_HWGRAD1_TARGET")) : 512;
-    long chunks = target1 / p.ydim; if (chunks < 1) chunks = 1; if (chunks > p.n_tiles) chunks = p.n_tiles;
+    long chunks = WGRAD_TARGET_BLOCKS / p.ydim; if (chunks < 1) chunks = 1; if (chunks > p.n_tiles) chunks = p.n_tiles;
     return wgrad_plan_finish(p, 1, WG_F_HGRAD, 0, co_b, ci_b, chunks, taps, Cout, Cin, M);
   }
   const int amma = mma >= 3 ? mma : ((taps == 27 && mma) ? 2 : 0);   // 1 / 2: bf16 operands (gradients: range); 3: split-bf16 (fp32-accurate)
@@ -2428,16 +2412,14 @@ int wgrad_plan(int entry, int taps, int NV, int D3, int H, int W, int Cin, int C
     // narrow planes (W not a multiple of 16): flat-position tiles for the fp32 / reduced-precision kernels.  In split-bf16 mode
     // the rectangular 8 x 16 tiles of wgrad_split_kernel are taken instead, ragged last column of tiles and all (W = 40: 17 %
     // of the MFMA rows idle, W = 20 / 10: 37 %) - six bf16 MFMAs per 32 pixels still beat eight fp32 MFMAs per 16 by more than
-    // that (A/B knob ARCO_WGRAD_FLAT_SPLIT=0: round 2's choice, the fp32 flat-tile kernel)
-    static const int flat_split = getenv("ARCO_WGRAD_FLAT_SPLIT") ? atoi(getenv("ARCO_WGRAD_FLAT_SPLIT")) : 1;
+    // that (the fp32 flat-tile kernel was the earlier choice there)
     const bool split_ok = amma == 3 && (Cout & 3) == 0 && (Cin & 3) == 0 && (ld_dz & 3) == 0 && (ld_in & 3) == 0;
-    p.flat = (W & 15) != 0 && W + 2 <= IGEMM_FLAT_WPMAX && !(split_ok && flat_split && W >= 10);
+    p.flat = (W & 15) != 0 && W + 2 <= IGEMM_FLAT_WPMAX && !(split_ok && W >= 10);
     if (p.flat) p.n_tiles = NB * ((H * (W + 2) + 127) / 128);
     p.zdim = taps / 9; p.ydim = (p.CoutPad / hco) * (p.CinPad / hci);
     // 32x32 blocks run persistent (2 workgroups per CU, several tiles each); the others one slab per ~tile
     // (16 x 32 blocks of the split kernel: 60.7 KB of LDS, two per CU as well - 768 left a third round at half occupancy)
-    static const long target_env = getenv("ARCO_WGRAD_TARGET") ? atol(getenv("ARCO_WGRAD_TARGET")) : 0;     // A/B knob (<= the defaults: the slab reservation)
-    const long target = target_env > 0 ? target_env : ((hci == 32 && (hco == 32 || amma == 3)) ? 512 : 768);
+    const long target = (hci == 32 && (hco == 32 || amma == 3)) ? WGRAD_TARGET_BLOCKS : 768;
     long chunks = target / ((long)p.zdim * p.ydim); if (chunks > p.n_tiles) chunks = p.n_tiles;
     const bool split = split_ok && !p.flat;
     if (pro_on && !split) return ARCO_ERR_UNSUPPORTED;
@@ -2445,29 +2427,25 @@ int wgrad_plan(int entry, int taps, int NV, int D3, int H, int W, int Cin, int C
     p.bf16 = amma == 2;
     return wgrad_plan_finish(p, 9, WG_F_HALO, (p.flat ? 1 : 0) + (p.bf16 ? 2 : 0), hco, hci, chunks, taps, Cout, Cin, M);
   }
-  {   // wide 1x1 gradients over many pixels: 128 x 128 blocks, one workgroup per CU (wgrad_q_kernel); A/B knob ARCO_WGRAD_Q=0
-    static const int wq = getenv("ARCO_WGRAD_Q") ? atoi(getenv("ARCO_WGRAD_Q")) : 1;
+  {   // wide 1x1 gradients over many pixels: 128 x 128 blocks of 64-pixel tiles, two workgroups per CU (wgrad_q_kernel)
     const int cop = (Cout + 127) / 128 * 128, cip = (Cin + 127) / 128 * 128;
     const long yzq = (long)(cop / 128) * (cip / 128);
     const long reserved = arco_wgrad_ws_floats(Cout, Cin, taps, M);
     long chq = 256 / yzq; if (chq < 1) chq = 1; if (chq > p.n_tiles) chq = p.n_tiles;
-    if (wq && taps == 1 && Cout >= 192 && Cin >= 192 && M >= 32768 && (Cout & 3) == 0 && (Cin & 3) == 0 &&
+    if (taps == 1 && Cout >= 192 && Cin >= 192 && M >= 32768 && (Cout & 3) == 0 && (Cin & 3) == 0 &&
         (ld_dz & 3) == 0 && (ld_in & 3) == 0 && aligned16 && chq * cop * cip <= reserved) {
       p.CoutPad = cop; p.CinPad = cip;
       p.ydim = cop / 128; p.zdim = cip / 128;
-      static const int tp = getenv("ARCO_WGRAD_Q_TP") ? atoi(getenv("ARCO_WGRAD_Q_TP")) : 64;
-      if (tp == 64) {
-        p.n_tiles = (int)((M + 63) / 64);
-        long ch2 = 512 / yzq; if (ch2 < 1) ch2 = 1; if (ch2 > p.n_tiles) ch2 = p.n_tiles;
-        if (ch2 * cop * cip <= reserved) chq = ch2;
-      }
-      return wgrad_plan_finish(p, 1, WG_F_Q, 0, 0, tp == 64 ? 64 : 128, chq, taps, Cout, Cin, M);
+      p.n_tiles = (int)((M + 63) / 64);
+      long ch2 = WGRAD_TARGET_BLOCKS / yzq; if (ch2 < 1) ch2 = 1; if (ch2 > p.n_tiles) ch2 = p.n_tiles;
+      if (ch2 * cop * cip <= reserved) chq = ch2;
+      return wgrad_plan_finish(p, 1, WG_F_Q, 0, 0, 64, chq, taps, Cout, Cin, M);
     }
   }
   p.ydim = p.CoutPad / co_b; p.zdim = (p.CinPad / ci_b) * taps;
   const long yz = (long)p.ydim * p.zdim;
-  static const long target1 = getenv("ARCO_WGRAD1_TARGET") ? atol(getenv("ARCO_WGRAD1_TARGET")) : 512;   // two resident workgroups per CU, 6-13 tiles each (2048: 3 tiles each, a third of them behind an exposed first fetch; 4x the slabs)
-  long chunks = target1 / yz; if (chunks < 1) chunks = 1; if (chunks > p.n_tiles) chunks = p.n_tiles;
+  // two resident workgroups per CU, 6-13 tiles each (2048: 3 tiles each, a third of them behind an exposed first fetch; 4x the slabs)
+  long chunks = WGRAD_TARGET_BLOCKS / yz; if (chunks < 1) chunks = 1; if (chunks > p.n_tiles) chunks = p.n_tiles;
   return wgrad_plan_finish(p, 1, WG_F_GEMM, 0, co_b, ci_b, chunks, taps, Cout, Cin, M);
 }
 
@@ -2586,17 +2564,10 @@ static int conv3d_wgrad_impl(const float* dZ, long ld_dz, int Cout, const float*
 #undef WS
 #undef WH
   } else if (p.family == WG_F_Q) {
-    if (p.cib == 64) {
-      constexpr int shq = 64 * (2 * (128 + WGRAD1_PAD)) * 4;
-      static unsigned long long attr_q = 0;
-      if (arco_first_on_device(attr_q)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_q_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, shq); }
-      hipLaunchKernelGGL(wgrad_q_kernel<64>, dim3((unsigned)chunks, p.ydim, p.zdim), dim3(256), shq, st, a);
-    } else {
-      constexpr int shq = 128 * (2 * (128 + WGRAD1_PAD)) * 4;
-      static unsigned long long attr_q = 0;
-      if (arco_first_on_device(attr_q)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_q_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, shq); }
-      hipLaunchKernelGGL(wgrad_q_kernel<128>, dim3((unsigned)chunks, p.ydim, p.zdim), dim3(256), shq, st, a);
-    }
+    constexpr int shq = 64 * (2 * (128 + WGRAD1_PAD)) * 4;
+    static unsigned long long attr_q = 0;
+    if (arco_first_on_device(attr_q)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_q_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, shq); }
+    hipLaunchKernelGGL(wgrad_q_kernel<64>, dim3((unsigned)chunks, p.ydim, p.zdim), dim3(256), shq, st, a);
   } else {
     const int co_b = p.cob, ci_b = p.cib;
     dim3 grid((unsigned)chunks, p.ydim, p.zdim);

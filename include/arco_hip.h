@@ -156,17 +156,17 @@ int arco_conv_config_mma(int taps, int NB, int H, int W, int Cin, int Cout, long
  * volume runs on conv3d_image_kernel<3> in mma 4 too and reports 27701016.  A call rejected with ARCO_ERR_ARG leaves it unchanged.
  * Host side only: nothing on the device changes. */
 int arco_conv_last_route(void);
-/* A/B switch of the software-pipelined split-bf16 3x3 kernel (conv_sp.hip; ids 9.3e6 + A_T*1e3 + BN, resident-weights form 9.35e6 + ...): on = 1 (default,
- * or ARCO_CONV_SP=0 in the environment for off) lets the eligible wide 2-D shapes take it, 0 keeps every shape on
+/* A/B switch of the software-pipelined split-bf16 3x3 kernel (conv_sp.hip; ids 9.3e6 + A_T*1e3 + BN, resident-weights form 9.35e6 + ...): on = 1
+ * (default) lets the eligible wide 2-D shapes take it, 0 keeps every shape on
  * igemm_kernel.  Returns the previous setting.  Tile counts differ: query arco_conv_mblocks_mma after switching.   */
 int arco_conv_sp_set(int on);
-/* A/B switch of the software-pipelined flat-tile 3x3x3 kernel (conv3d_fl.hip; ids 9.27e6 / 9.28e6 / 9.29e6 + A_T*1e3 + BN for its per-step, depth-walking and per-chunk forms: the 32 .. 256-channel levels of
- * the V-Net, vnetWithArgs.py:5-31): on = 0 (or ARCO_CONV3D_FL=0) keeps every 3x3x3 launch on igemm_kernel.  Outputs are bit-identical
+/* A/B switch of the software-pipelined flat-tile 3x3x3 kernel (conv3d_fl.hip; ids 9.27e6 / 9.29e6 + A_T*1e3 + BN for its per-step and per-chunk forms: the 32 .. 256-channel levels of
+ * the V-Net, vnetWithArgs.py:5-31): on = 0 keeps every 3x3x3 launch on igemm_kernel.  Outputs are bit-identical
  * either way; tile counts differ (query arco_conv_mblocks_mma after switching).  Returns the previous setting. */
 int arco_conv3d_fl_set(int on);
 /* A/B switch of the software-pipelined split-bf16 1x1 GEMM (gemm_sp.hip; the wide many-tile FeatureExtractor / q_representation GEMMs,
- * model_2D.py:20-55, train_arco_2d.py:231-234): on = 0 (or ARCO_GEMM_SP=0) keeps every GEMM on igemm_kernel; min_tiles > 0 also sets the
- * smallest 128 x 128 tile count the kernel takes (default 2048, ARCO_GEMM_SP_TILES).  Outputs are bit-identical either way.  Returns the
+ * model_2D.py:20-55, train_arco_2d.py:231-234): on = 0 keeps every GEMM on igemm_kernel; min_tiles > 0 also sets the
+ * smallest 128 x 128 tile count the kernel takes (default 2048).  Outputs are bit-identical either way.  Returns the
  * previous `on`. */
 int arco_gemm_sp_set(int on, long min_tiles);
 /* out = W . in + trilinear_align_corners(lo): the 1x1x1 conv over a high-resolution feature map with the upsampled low-resolution
@@ -201,7 +201,7 @@ long arco_wgrad_ws_floats(int Cout, int Cin, int taps, long M);
  * 16 and ld_dz a multiple of 4): any other such shape is ARCO_ERR_UNSUPPORTED, in the query and in the launch.
  * Ids: T*1e6 + F*1e5 + V*1e4 + COB*100 + CIB, T = 1 (taps 1) or 9 (taps 9 and 27), COB x CIB the channel tile:
  *   F 0  wgrad_kernel<COB,CIB>                  1001616 .. 1006464
- *   F 1  wgrad_q_kernel<TP>                     1100064, 1100128 (TP in the CIB field)
+ *   F 1  wgrad_q_kernel<64>                     1100064 (the pixels per staged tile in the CIB field)
  *   F 2  wgrad_halo2_kernel<COB,CIB,FLAT,MODE>  V = FLAT + 2 * (bf16 operands): 9201616 rectangular fp32, 9211616 flat fp32, 9221616, 9231616
  *   F 3  wgrad_split_kernel<COB,CIB,PRO>        V = PRO: 9301616 .. 9303232, 9311616 .. 9313232
  *   F 4  wgrad_image3d_kernel<DEPTH>            V = DEPTH: 9411616, 9431616

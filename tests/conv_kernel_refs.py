@@ -125,7 +125,7 @@ CASES_3X3 += [
     C("halo-32-32-rounds", 9, 0, 2, 1, 64, 520, 32, 32, 9932032, "mfma0", res=True, stats=2),
     C("image-k3-rounds", 9, 0, 5, 1, 240, 250, 3, 16, 9803016, "image", bias=True, stats=1),
 ]
-# conv_sp.hip (mma 3): launch_sp<A_T, C_T> (ids 9.3e6 + A_T 1e3 + 16 C_T) needs ARCO_CONV_SP_TILES = 192 work items; C_T = 1 exists only
+# conv_sp.hip (mma 3): launch_sp<A_T, C_T> (ids 9.3e6 + A_T 1e3 + 16 C_T) needs CONV_SP_MIN_TILES = 192 work items; C_T = 1 exists only
 # with A_T = 4 (dispatch_rows<1> is never called: <2,1> and <1,1> are unreachable).  launch_rw: 9.35e6 + rows / 4 * 1e3 + BN.
 CASES_3X3 += [
     C("sp-4-4", 9, 3, 5, 1, 128, 128, 16, 64, 9304064, "mfma3", bias=True, stats=1),

@@ -41,10 +41,9 @@ N = 19 / 4 / 2, K = 20 / 48, one image and one single-plane volume (NV D3 = 1: c
 conv3d_fc_kernel, one dispatch_spatial<3> and one flat tile), and more tiles than workgroups with a ragged last round on every
 persistent kernel.
 Not covered, and why: launch_sp<2,1> and <1,1> (dispatch_rows<1> is never called: unreachable); gemm_sp_kernel at N = 64 (its padding
-rule refuses Npad < 208 at any tile threshold: the case asserts igemm_kernel<1,32,64>); routes that only an environment variable read
-once per process opens (ARCO_IGEMM_256's 256x32 flat tile, ARCO_GEMM224's alternatives, ARCO_CONV3D_DW's conv3d_dw_kernel, the forced
-ARCO_CONV3D_FL_CFG forms incl. the eight-wave conv3d_fc_kernel<..,8>, ARCO_CONV_RW8 < 2: launch_rw<8,1>, <4,2>).  The largest 3x3x3
-tiles (50176 .. 65536 voxels) run the fixed and the wide kind only; their smaller siblings run all four.
+rule refuses Npad < 208 at any tile threshold: the case asserts igemm_kernel<1,32,64>); the tile shapes of conv3d_fl.hip that fl_cost
+picks at no plane width of this file and only a forced ARCO_CONV3D_FL_CFG reaches (tests/test_conv3d_fl_gpu.py runs each of them).  The
+largest 3x3x3 tiles (50176 .. 65536 voxels) run the fixed and the wide kind only; their smaller siblings run all four.
 Out of scope: the weight-gradient kernels, the BatchNorm family, conv_h.hip (mma 4) and the opt-in mma 1 / 2, arco_conv3d_fwd_pro
 (tests/test_block_fuse_gpu.py ties it bit for bit to the two-pass route that this file anchors)."""
 import contextlib

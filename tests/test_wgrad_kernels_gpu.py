@@ -39,7 +39,7 @@ a step below its M and Cin thresholds; wgrad_halo2_kernel rectangular and flat i
 the fall-back of mma 3; wgrad_split_kernel in four tiles at taps 9 and 27 with and without the consumer-side activation;
 wgrad_image3d_kernel<1|3> (fp32 and f16 dZ); hwgrad_kernel<.,.,9> in four tiles at taps 9 and 27 and <.,.,1> in nine;
 himage_wgrad_kernel at K = 1 .. 4; the three slab reductions at 1, 16 and 17 slabs; the three branches of colsum_partial_kernel for
-float and f16; transpose2d_kernel.  Unreachable without an environment variable read once per process: wgrad_kernel_refs.UNREACHABLE."""
+float and f16; transpose2d_kernel."""
 import ctypes
 
 import pytest

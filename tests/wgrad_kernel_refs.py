@@ -207,12 +207,6 @@ PRO_UNSUPPORTED = [("taps27", 27, 3, 2, 2, 16, 16, 16, 16, 16, 2), ("flat", 9, 3
 # hwgrad_dispatch / arco_conv3x3_image_wgrad_h rejections (taps, cin, cout, ld_dz, ld_in)
 H_UNSUPPORTED = [("cin&7", 9, 12, 16, 16, 16), ("ld_in&7", 9, 16, 16, 16, 20), ("ldz-odd-27", 27, 16, 19, 19, 16), ("ldz-odd-1", 1, 16, 19, 19, 16),
                  ("cin1-cout20", 9, 1, 20, 20, 1), ("cin1-ldz-odd", 27, 1, 16, 18, 1)]      # f16 dZ, fp32 volume: wgrad_image3d_kernel or nothing
-# routes that no shape reaches without an environment variable read once per process
-UNREACHABLE = ["wgrad_q_kernel<128> (ARCO_WGRAD_Q_TP != 64)",
-               "wgrad_halo2_kernel flat tiles in mma 3 at W >= 10 on aligned operands (ARCO_WGRAD_FLAT_SPLIT=0)",
-               "slab targets other than 768 / 512 (ARCO_WGRAD_TARGET, ARCO_WGRAD1_TARGET, ARCO_HWGRAD_TARGET, ARCO_HWGRAD1_TARGET)",
-               "wgrad_reduce_kernel<16,32> on shapes wgrad_reduce4_kernel takes (ARCO_WGRAD_REDUCE4=0)",
-               "wgrad_kernel on the wgrad_q shapes (ARCO_WGRAD_Q=0)"]
 
 
 def by_name(name):

@@ -1,6 +1,6 @@
 """f16-storage convolution launches for PMC passes (HBM bytes, LDS bank conflicts): 5 launches per class, a 256 MB tensor touched
-between launches.  Classes at the LiTS shard's shapes (2 volumes): 16->16 @160x160x96 (hconv_rw_kernel, or hconv_kernel<9,128,16>
-with ARCO_HCONV_RW=0) | 32->32 @80x80x48 (hconv_kernel<9,128,32>) | 64->64 @40x40x24 (flat tiles) | weight gradient 32->32 @80x80x48"""
+between launches.  Classes at the LiTS shard's shapes (2 volumes): 16->16 @160x160x96 (hconv_rw_kernel)
+| 32->32 @80x80x48 (hconv_kernel<9,128,32>) | 64->64 @40x40x24 (flat tiles) | weight gradient 32->32 @80x80x48"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
