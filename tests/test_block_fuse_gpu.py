@@ -3,7 +3,8 @@ convolution (arco_conv3d_fwd_pro) and of its weight gradient (arco_conv3d_wgrad_
 
 The loaders evaluate arco_bn_act_fwd's arithmetic operation for operation, so every comparison here is BIT-EXACT against the
 two-pass route (BN-apply pass writing the activation, plain convolution reading it): kernel by kernel on every pipelined kernel
-instantiation the U-Net uses, block by block, and over the whole U-Net forward + backward (-m gpu)."""
+instantiation the U-Net uses, block by block, and over the whole U-Net forward + backward (-m gpu).  The BatchNorm half of that
+two-pass route (arco_bn_act_fwd and the kernels around it) is itself held to float64 in tests/test_norm_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch

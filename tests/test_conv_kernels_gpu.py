@@ -44,7 +44,8 @@ Not covered, and why: launch_sp<2,1> and <1,1> (dispatch_rows<1> is never called
 rule refuses Npad < 208 at any tile threshold: the case asserts igemm_kernel<1,32,64>); the tile shapes of conv3d_fl.hip that fl_cost
 picks at no plane width of this file and only a forced ARCO_CONV3D_FL_CFG reaches (tests/test_conv3d_fl_gpu.py runs each of them).  The
 largest 3x3x3 tiles (50176 .. 65536 voxels) run the fixed and the wide kind only; their smaller siblings run all four.
-Out of scope: the weight-gradient kernels, the BatchNorm family, conv_h.hip (mma 4) and the opt-in mma 1 / 2, arco_conv3d_fwd_pro
+Out of scope: the weight-gradient kernels, the BatchNorm / GroupNorm family (held to float64 kernel by kernel in
+tests/test_norm_kernels_gpu.py), conv_h.hip (mma 4) and the opt-in mma 1 / 2, arco_conv3d_fwd_pro
 (tests/test_block_fuse_gpu.py ties it bit for bit to the two-pass route that this file anchors)."""
 import contextlib
 import struct
