@@ -321,6 +321,7 @@ static int launch_hconv(const IgemmArgs& a, hipStream_t st, int* q) {
   IgemmArgs b = a;
   b.n_mblocks = mblocks;
   b.n_nblocks = (a.Npad + BN - 1) / BN;
+  arco_note_route(TAPS * 1000000 + BM * 1000 + BN + (FLAT ? 500000 : 0));      // (2-D and 3-D tiles share ids: the call's taps tells them apart)
   hipLaunchKernelGGL(kern, dim3((unsigned)(mblocks * b.n_nblocks)), dim3(256), sh, st, b);
   return arco_launch_status();
 }
@@ -567,6 +568,7 @@ static int launch_hconv_rw(const IgemmArgs& a, hipStream_t st, int* q) {
   IgemmArgs b = a;
   b.n_mblocks = (int)(a.NB * tiles);
   const long grid = slots < units ? slots : units;
+  arco_note_route(9 * 1000000 + 400000 + TH * 1000 + C_T * 16);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NT), G::LDS_BYTES, st, b, S, nseg);
   return arco_launch_status();
 }
@@ -835,6 +837,7 @@ static int launch_hfc(const IgemmArgs& a, hipStream_t st, int* q) {
   auto kern = hconv_fc_kernel<A_T, C_T>;
   static unsigned long long attr_set = 0;
   if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
+  arco_note_route(9260000 + A_T * 1000 + G::BN);
   hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(512), lds, st, b);
   return arco_launch_status();
 }
@@ -964,12 +967,14 @@ static int hconv1x1_stream_dispatch(const IgemmArgs& a, hipStream_t st) {
     if (Q == 1) hipLaunchKernelGGL(hconv1x1_narrow_out_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, a);
     else if (Q == 2) hipLaunchKernelGGL(hconv1x1_narrow_out_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(hconv1x1_narrow_out_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    arco_note_route(1800000 + a.K * 1000 + 4);      // (launch-only routes: ids beside the others in include/arco_hip.h)
     return arco_launch_status();
   }
   if (a.K >= 1 && a.K <= 4 && (a.N == 8 || a.N == 16 || a.N == 32) && (a.ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0) {
     const int Q = a.N / 8;
     blocks = (a.M + (256 / Q) * 8 - 1) / ((256 / Q) * 8); if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(hconv1x1_narrow_in_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    arco_note_route(1900000);
     return arco_launch_status();
   }
   return -1;

@@ -2033,8 +2033,8 @@ extern "C" {
 
 // Test-facing: the id (as arco_conv_config_mma reports it) of the kernel that the most recent forward launch of this thread took.  Every
 // forward entry point sets it to 0 once its arguments have passed, so it is 0 before the first launch, after a call that found no
-// kernel (ARCO_ERR_UNSUPPORTED) and after a launch through conv_h.hip (mma 4), whose kernels do not note theirs; a call rejected
-// with ARCO_ERR_ARG leaves it unchanged.
+// kernel (ARCO_ERR_UNSUPPORTED); the kernels of conv_h.hip (mma 4) note theirs like the others.  A call rejected with ARCO_ERR_ARG
+// leaves it unchanged - the alignment checks of hconv_dispatch, which run after the reset, put the previous id back.
 int arco_conv_last_route(void) { return arco_last_route; }
 
 // Query: number of M-blocks (= BN-stat partial slabs per channel) the conv launch will use.
@@ -2297,6 +2297,7 @@ static int conv3d_fwd_impl(const float* in, long ld_in, int K, const float* Wp, 
     a.Kpad = taps == 1 ? a.Kg * 16 : (K + 15) / 16 * 16;
   }
   ARCO_CHECK_ARG(NV % a.stat_groups == 0);
+  const int prev_route = arco_last_route;
   arco_note_route(0);
   if (pro && taps == 27) {      // (arco_conv_pro_ok has vouched for the shape: conv3d_fc_kernel<.., PRO>)
     a.pro = *pro;
@@ -2311,7 +2312,9 @@ static int conv3d_fwd_impl(const float* in, long ld_in, int K, const float* Wp, 
   if (mma == 4) {       // f16 activation storage: `out` (and `in`, unless this is the one-channel fp32 volume of the first layer) are f16
     if (taps == 27 && image_conv3d_eligible(a)) return launch_image_conv3d<3>(a, as_stream(stream), nullptr);
     a.Kpad = (K + 31) / 32 * 32;
-    return hconv_dispatch(a, taps, as_stream(stream), nullptr);
+    const int r = hconv_dispatch(a, taps, as_stream(stream), nullptr);
+    if (r == ARCO_ERR_ARG) arco_note_route(prev_route);      // (its pointer-alignment checks: a rejected call notes nothing)
+    return r;
   }
   return dispatch_igemm(a, taps, as_stream(stream), nullptr);
 }

@@ -146,14 +146,20 @@ int arco_conv_mblocks_pro(int taps, int NB, int H, int W, int Cin, int Cout, lon
  * Launch-only routes, which no query describes and only arco_conv_last_route reports:
  *   conv1x1_narrow_out_kernel<Q> -> 1.6e6 + K*1e3 + 4 (K = 4 Q = 4, 8, 16, 32: 1604004, 1608004, 1616004, 1632004)
  *   conv1x1_narrow_in_kernel     -> 1700000
- *   gemm_sp_kernel<false>        -> 1464256 (1e6 + 4e5 + BM*1e3 + BN, 64 x 256 tiles);  gemm_sp_kernel<true> (fused upsample) -> 1514256 */
+ *   gemm_sp_kernel<false>        -> 1464256 (1e6 + 4e5 + BM*1e3 + BN, 64 x 256 tiles);  gemm_sp_kernel<true> (fused upsample) -> 1514256
+ *   hconv1x1_narrow_out_kernel<Q> (mma 4) -> 1.8e6 + K*1e3 + 4 (K = 8 Q = 8, 16, 32: 1808004, 1816004, 1832004)
+ *   hconv1x1_narrow_in_kernel     (mma 4) -> 1900000
+ * The f16-storage kernels of conv_h.hip (mma 4): hconv_kernel<TAPS,BM,BN,..> -> TAPS*1e6 + BM*1e3 + BN with the kernel-tap form 9 for
+ * 3x3 AND 3x3x3 (flat 3x3x3 tiles add 5e5), so the 2-D and the 3-D instantiation of one tile share an id and the `taps` argument of
+ * the call tells them apart; hconv_rw_kernel<1,1,8> -> 9408016; hconv_fc_kernel<A_T,C_T> -> 9.26e6 + A_T*1e3 + 16 C_T. */
 int arco_conv_config(int taps, int NB, int H, int W, int Cin, int Cout, long ld_in, int* kc_depth_db);
 int arco_conv_config_mma(int taps, int NB, int H, int W, int Cin, int Cout, long ld_in, int mma);
 /* test-facing: the id, as above, of the kernel that the most recent forward launch on the calling thread took (arco_conv_fwd,
  * arco_conv3d_fwd(_pro), arco_gemm_splitk, arco_gemm_batched, arco_conv1x1_upres_fwd).  Each of these sets it to 0 once its arguments
  * have passed: it is 0 before the first launch, after a call that found no kernel (ARCO_ERR_UNSUPPORTED, such as a refused
- * arco_conv1x1_upres_fwd) and after a launch on the kernels of conv_h.hip (mma 4), which do not note theirs - the one-channel 3x3x3
- * volume runs on conv3d_image_kernel<3> in mma 4 too and reports 27701016.  A call rejected with ARCO_ERR_ARG leaves it unchanged.
+ * arco_conv1x1_upres_fwd).  The kernels of conv_h.hip (mma 4) note their ids too (listed above; the two streaming kernels are
+ * launch-only); the one-channel 3x3x3 volume runs on conv3d_image_kernel<3> in mma 4 as well and reports 27701016.  A call rejected
+ * with ARCO_ERR_ARG - the pointer-alignment checks of mma 4 included - leaves it unchanged.
  * Host side only: nothing on the device changes. */
 int arco_conv_last_route(void);
 /* A/B switch of the software-pipelined split-bf16 3x3 kernel (conv_sp.hip; ids 9.3e6 + A_T*1e3 + BN, resident-weights form 9.35e6 + ...): on = 1

@@ -3,7 +3,8 @@ entry points) against the fp32 kernels of the same operators AND float64 PyTorch
 the convention of tests/test_half_gpu.py: products of f16 values are exact in fp32 and accumulation is fp32 in both, so what differs
 is one rounding of each stored result (2^-11 relative): stored results are held to 1e-3 of the tensor's maximum, fp32 weight / bias
 gradients (exact products, another summation order) to 2e-5.  Reference operators: nn.Conv2d / BatchNorm2d / LeakyReLU / Dropout /
-MaxPool2d / Upsample(bilinear, align_corners) of unetWithArgs.py:31-85."""
+MaxPool2d / Upsample(bilinear, align_corners) of unetWithArgs.py:31-85.
+The per-element float64 anchor of the 3x3 / 1x1 forward and data-gradient kernels, route by route, lives in tests/test_hconv_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch

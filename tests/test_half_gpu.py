@@ -1,7 +1,8 @@
 """f16 ACTIVATION STORAGE of the volume path (BASELINE.json configs[4], "fp16 MFMA conv"; csrc/conv_h.hip, the *_h entry points)
 against the fp32 kernels of the same operators on the SAME f16-representable inputs: what differs is only the rounding of the
 stored outputs (2^-11 relative) - products are exact in both (f16 x f16 fits fp32), accumulation is fp32 in both.  Tolerances are
-written per test.  Reference operators: nn.Conv3d / BatchNorm3d / ReLU / ConvTranspose3d of vnetWithArgs.py:5-31,67-118."""
+written per test.  Reference operators: nn.Conv3d / BatchNorm3d / ReLU / ConvTranspose3d of vnetWithArgs.py:5-31,67-118.
+The per-element float64 anchor of the forward and data-gradient kernels, route by route, lives in tests/test_hconv_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch
