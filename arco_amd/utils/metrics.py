@@ -63,6 +63,12 @@ def cal_dice(prediction, label, num=2):
     return total_dice
 
 
-def calculate_metric_percase(pred, gt):
-    """(dice, jaccard, hd95, asd) of two binary masks (utils/metrics.py:20-26, test_util.py:214-220)."""
+def calculate_metric_percase(pred, gt, surface="host"):
+    """(dice, jaccard, hd95, asd) of two binary masks (utils/metrics.py:20-26, test_util.py:214-220).  surface="gpu" takes hd95 / asd
+    from the HIP surface-distance kernels (utils/surface_gpu.py) instead of scipy on the host."""
+    if surface not in ("host", "gpu"):
+        raise ValueError(f"surface must be 'host' or 'gpu', got {surface!r}")
+    if surface == "gpu":
+        from . import surface_gpu            # (imported here: the host route of this module needs numpy and scipy only)
+        return (binary.dc(pred, gt), binary.jc(pred, gt)) + surface_gpu.pair_metrics(pred, gt)
     return binary.dc(pred, gt), binary.jc(pred, gt), binary.hd95(pred, gt), binary.asd(pred, gt)

@@ -1,0 +1,146 @@
+"""hd95 / asd on the GPU: the surface distances of utils/metrics.py (medpy.metric.binary restated) for unit voxel spacing and
+connectivity 1 - the only way the reference calls them (test_2D.py:52-66, test_util.py:214-220) - as HIP kernels (csrc/surface.hip).
+
+With unit spacing every squared surface distance is an integer, so the device returns a HISTOGRAM of squared distances
+  hist[class][direction][k],  direction 0 = border(pred) -> border(gt), 1 = border(gt) -> border(pred),
+  k = 0 .. (D-1)^2 + (H-1)^2 + (W-1)^2
+computed in integer arithmetic (exact, independent of the order of arrival).  Only the non-empty bins travel to the host, which
+finishes in float64 with numpy's own percentile:
+  v = repeat(sqrt(k), count);  hd95 = percentile(v of both directions pooled, 95);  asd = mean(v of direction 0)
+sqrt of the integer k is bit for bit what distance_transform_edt returns at that voxel, so hd95 equals the host route exactly and asd
+up to the order of one float64 sum.  Anisotropic spacing breaks the integer histogram: that stays with the host route (utils/metrics.py)."""
+import numpy as np
+import torch
+
+from .. import _lib as L
+
+MAX_DIM = 4096          # csrc/surface.hip SF_MAXDIM
+MAX_CLASSES = 32        # csrc/surface.hip SF_MAXCLS
+ROUTES = ("host", "gpu")
+
+_EMPTY = ('The first supplied array does not contain any binary object.',
+          'The second supplied array does not contain any binary object.')      # metrics.binary._surface_distances
+
+
+def check_route(surface):
+    """The `surface=` keyword of the evaluation entry points: "host" (utils/metrics.py, scipy) or "gpu" (this module)."""
+    if surface not in ROUTES:
+        raise ValueError(f"surface must be one of {ROUTES}, got {surface!r}")
+    return surface
+
+
+def nbins(shape):
+    """Bins of one histogram row for a volume of `shape`: the largest squared distance plus one."""
+    return int(sum((int(s) - 1) ** 2 for s in shape)) + 1
+
+
+def _class_range(classes):
+    cls = [int(c) for c in classes]
+    if not cls or cls != list(range(cls[0], cls[0] + len(cls))):
+        raise ValueError(f"classes must be a non-empty contiguous ascending range, got {list(classes)!r}")
+    if len(cls) > MAX_CLASSES:
+        raise ValueError(f"at most {MAX_CLASSES} classes per call, got {len(cls)}")
+    return cls[0], cls[-1]
+
+
+def surface_histograms(pred, gt, classes, ndim=None):
+    """int64 [len(classes), 2, nbins(shape)] on the device for two integer label tensors (2-D or 3-D, same shape, on the GPU).
+    ndim (default: the tensors' rank) says how many axes have neighbours: a [1, H, W] tensor with ndim=2 is the 2-D map [H, W], and
+    an [H, W] tensor with ndim=3 is the one-slice volume [1, H, W], whose every voxel is a border voxel (its z neighbours lie outside)."""
+    c_lo, c_hi = _class_range(classes)
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)):
+        raise TypeError("surface_histograms takes torch tensors on the GPU")
+    if pred.dtype.is_floating_point or gt.dtype.is_floating_point or pred.dtype == torch.bool or gt.dtype == torch.bool:
+        raise TypeError("surface_histograms takes integer label tensors")
+    if pred.shape != gt.shape:
+        raise ValueError(f"shapes differ: {tuple(pred.shape)} vs {tuple(gt.shape)}")
+    if pred.dim() not in (2, 3):
+        raise ValueError(f"label maps must be 2-D or 3-D, got shape {tuple(pred.shape)}")
+    ndim = pred.dim() if ndim is None else int(ndim)
+    if ndim not in (2, 3) or (ndim == 2 and pred.dim() == 3 and pred.shape[0] != 1):
+        raise ValueError(f"ndim must be 2 or 3, and 2 only for a map [H, W] or [1, H, W]; got shape {tuple(pred.shape)} and ndim {ndim}")
+    if min(pred.shape) < 1 or max(pred.shape) > MAX_DIM:
+        raise ValueError(f"every dim must be in 1..{MAX_DIM}, got {tuple(pred.shape)}")
+    L.require_gpu(pred, gt)
+    D, H, W = (1, *pred.shape) if pred.dim() == 2 else pred.shape
+    p = pred.to(torch.int64).contiguous()
+    g = gt.to(torch.int64).contiguous()
+    nc, nb = c_hi - c_lo + 1, nbins(pred.shape)
+    ws_bytes = L.query("arco_surface_ws_bytes", D, H, W, nc)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=p.device)
+    hist = torch.empty((nc, 2, nb), dtype=torch.int64, device=p.device)
+    with torch.cuda.device(p.device):
+        L.call("arco_surface_hist", L.ptr(p), L.ptr(g), D, H, W, ndim, c_lo, c_hi, L.ptr(ws), ws_bytes, L.ptr(hist), hist.numel() * 8)
+    return hist
+
+
+def _distances(bins, counts):
+    return np.repeat(np.sqrt(np.asarray(bins).astype(np.float64)), np.asarray(counts))
+
+
+def finish(bins0, counts0, bins1, counts1):
+    """(hd95, asd) in float64 from the non-empty bins of the two directions; None when a direction is empty."""
+    v0, v1 = _distances(bins0, counts0), _distances(bins1, counts1)
+    if v0.size == 0 or v1.size == 0:
+        return None
+    return float(np.percentile(np.hstack((v0, v1)), 95)), float(v0.mean())
+
+
+def finish_histogram(hist):
+    """`finish` for one class's dense histogram [2, nbins] (a numpy array)."""
+    hist = np.asarray(hist)
+    b0, b1 = np.flatnonzero(hist[0]), np.flatnonzero(hist[1])
+    return finish(b0, hist[0][b0], b1, hist[1][b1])
+
+
+def surface_metrics(pred, gt, classes):
+    """[(hd95, asd) or None] per class; None where the class has no voxel in pred or in gt (the host functions raise
+    RuntimeError there and their callers guard for it)."""
+    hist = surface_histograms(pred, gt, classes)
+    nz = torch.nonzero(hist)                                            # [k, 3] = (class, direction, bin), row-major order
+    rec = torch.cat((nz, hist[nz[:, 0], nz[:, 1], nz[:, 2]].unsqueeze(1)), dim=1).cpu().numpy()
+    out = []
+    for c in range(hist.shape[0]):
+        r0 = rec[(rec[:, 0] == c) & (rec[:, 1] == 0)]
+        r1 = rec[(rec[:, 0] == c) & (rec[:, 1] == 1)]
+        out.append(finish(r0[:, 2], r0[:, 3], r1[:, 2], r1[:, 3]))
+    return out
+
+
+def _binary_args(voxelspacing, connectivity):
+    if voxelspacing is not None:
+        raise ValueError("the GPU surface metrics are for unit voxel spacing (voxelspacing=None); "
+                         "use the host route arco_amd.utils.metrics.binary for a voxelspacing")
+    if connectivity != 1:
+        raise ValueError("the GPU surface metrics are for connectivity 1; use the host route arco_amd.utils.metrics.binary "
+                         f"for connectivity {connectivity!r}")
+
+
+def _mask(x, device):
+    t = x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x) > 0)      # (a fresh bool array: one byte per voxel to upload)
+    if device is None:
+        device = t.device if t.is_cuda else "cuda:0"
+    return (t.to(device) > 0).to(torch.int64)
+
+
+def pair_metrics(result, reference, voxelspacing=None, connectivity=1, device=None):
+    """(hd95, asd) of one pair of binary masks (`> 0`; numpy or torch, 2-D or 3-D) from ONE histogram call.  Raises
+    metrics.binary's RuntimeError when a mask is empty."""
+    _binary_args(voxelspacing, connectivity)
+    a = _mask(result, device)
+    b = _mask(reference, a.device)
+    got = surface_metrics(a, b, (1,))[0]
+    if got is None:
+        any_a, any_b = torch.stack((a.any(), b.any())).cpu().tolist()
+        raise RuntimeError(_EMPTY[0] if not any_a else _EMPTY[1])
+    return got
+
+
+def hd95(result, reference, voxelspacing=None, connectivity=1, device=None):
+    """metrics.binary.hd95 on the GPU."""
+    return pair_metrics(result, reference, voxelspacing, connectivity, device)[0]
+
+
+def asd(result, reference, voxelspacing=None, connectivity=1, device=None):
+    """metrics.binary.asd on the GPU."""
+    return pair_metrics(result, reference, voxelspacing, connectivity, device)[1]

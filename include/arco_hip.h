@@ -451,6 +451,19 @@ int arco_eqv_loss_bwd(const float* P_, long ldp, const float* Q_, long ldq, cons
                       const double* ws, const float* g, float* dP, long ldo, void* stream);
 /* ---- V  evaluation (test_2D.py:52-66): out[c] = {|pred==c|, |gt==c|, |pred==c & gt==c|} as int64[C][3]          */
 int arco_overlap_counts(const int64_t* pred, const int64_t* gt, long n, int C, int64_t* out, void* stream);
+/* ---- V  exact surface distances behind hd95 / asd (medpy.metric.binary with unit voxel spacing and connectivity 1, test_2D.py:52-66,
+ *      test_util.py:214-220) of two contiguous label volumes [D][H][W], for every class c_lo..c_hi (mask = label == c) in one call:
+ *        border(X)[v] = X[v] and one of the 2*ndim face neighbours is unset or outside the array;
+ *        hist[c - c_lo][0][k] = #{v in border(pred == c) : squared distance from v to the nearest voxel of border(gt == c) is k},
+ *        hist[c - c_lo][1][k] = the same with pred and gt exchanged;  nbins = (D-1)^2 + (H-1)^2 + (W-1)^2 + 1 bins per row.
+ *      Integer arithmetic throughout: the counts do not depend on the order of arrival.  A class without a voxel in either map
+ *      gives two rows of zeros.  ndim 2: D must be 1 and the z neighbours do not exist (they are not background).  hist is zeroed
+ *      here; ws: arco_surface_ws_bytes(D, H, W, classes) bytes (two uint32 planes per class and direction; -1 for sizes the launch
+ *      rejects).  ARCO_ERR_ARG before anything is launched for: a null pointer, a dim < 1 or > 4096, ndim not 2 or 3, ndim 2 with
+ *      D != 1, c_hi < c_lo, more than 32 classes, ws_bytes or hist_bytes (classes * 2 * nbins * 8) too small.                    */
+long arco_surface_ws_bytes(int D, int H, int W, int nc);
+int arco_surface_hist(const int64_t* pred, const int64_t* gt, int D, int H, int W, int ndim, int c_lo, int c_hi, void* ws,
+                      long ws_bytes, int64_t* hist, long hist_bytes, void* stream);
 /* ---- A  mixing strategies of the unlabeled stream (augment.py:284-313 generate_unsup_data, masks :230-252; volumes
  *      augment_3d.py:182-257).  desc_host[B][8] = {y0, y1, x0, x1, z0, z1, sel_lo, sel_hi} in HOST memory (the host
  *      draws it; it travels in the kernel arguments); Z = 1 in 2-D; mode 0 cutmix, 1 cutout, 2 classmix; data NC[spatial] */
