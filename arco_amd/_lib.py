@@ -45,6 +45,7 @@ _SIGS = {
     "arco_pack_many": [_P, _I, _L, _P],
     "arco_overlap_counts": [_P, _P, _L, _I, _P, _P],
     "arco_surface_hist": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P],
+    "arco_cc_largest": [_P, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P],
     "arco_mix_unsup": [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
     "arco_label_presence": [_P, _I, _L, _P, _P],
     "arco_window_accumulate": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -180,6 +181,7 @@ _QUERIES = {   # plain host helpers returning sizes
     "arco_loss_slabs": ([_I], _L),
     "arco_seg_ws_doubles": ([_L, _I, _I], _L),
     "arco_surface_ws_bytes": ([_I, _I, _I, _I], _L),
+    "arco_cc_ws_bytes": ([_I, _I, _I], _L),
     # host-side native sampler replay (no GPU work)
     "arco_grid_sample": ([_P, _L, _L, _L, _I, _I, _P], _L),
     "arco_randint": ([_P, _L, _L, _L, _P], _L),

@@ -4,13 +4,18 @@ kernels, utils/surface_gpu.py: hd95 equal, asd to the order of one float64 sum; 
 the reference asks medpy for).  Any other value is a ValueError, raised before any GPU work.
 
   2-D (test_2D.py:52-92)       calculate_metric_percase_2d, test_single_volume
-  3-D (test_util.py:39-79,214) calculate_metric_percase_3d, test_all_case
+  3-D (test_util.py:39-79,214) calculate_metric_percase_3d, test_all_case, predict_case
+test_all_case also takes `cc="host"` (default: getLargestCC on the host for `nms`) or `cc="gpu"` (with surface="gpu" only: the label map
+stays on the device from the arg-max through the largest component, utils/cc_gpu.py, to the four metrics).
 Inference, the zoom round trip, the sliding window, the overlap counts and the empty-set conventions are those modules' own."""
 import numpy as np
 import torch
 
+from . import _lib as _L
+from . import glue as _glue
 from . import test_2D as _t2d
 from . import test_util as _t3d
+from .utils import cc_gpu as _cc_gpu
 from .utils import surface_gpu as _surface_gpu
 from .utils.metrics import binary as _binary
 
@@ -56,20 +61,92 @@ def calculate_metric_percase_3d(pred, gt, surface="host"):
     return (_binary.dc(pred, gt), _binary.jc(pred, gt)) + _surface_gpu.pair_metrics(pred, gt)
 
 
+@torch.no_grad()
+def predict_case(net, image, stride_xy, stride_z, patch_size, num_classes, batch=4, device="cuda:0"):
+    """The label map of test_util.test_single_case as an int64 tensor [w, h, d] that stays ON THE DEVICE: neither it nor the score map
+    is copied to the host.  The window loop is test_single_case's, restated (that module stays as it is): the same padding, the same
+    windows in the same order, the same arco_window_accumulate / arco_score_finalize launches and the same crop;
+    tests/test_eval_cc_gpu.py holds the two to each other (array_equal, ragged and padded volumes)."""
+    image = np.asarray(image)
+    w, h, d = image.shape
+    pads = []
+    for s, p in zip((w, h, d), patch_size):
+        tot = max(p - s, 0)
+        pads.append((tot // 2, tot - tot // 2))
+    add_pad = any(a + b > 0 for a, b in pads)
+    if add_pad:
+        image = np.pad(image, pads, mode='constant', constant_values=0)
+    ww, hh, dd = image.shape
+    px, py, pz = (int(v) for v in patch_size)
+    vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
+    C = int(num_classes)
+    score = torch.zeros((C, ww, hh, dd), dtype=torch.float32, device=device)
+    cnt = torch.zeros((ww, hh, dd), dtype=torch.float32, device=device)
+    starts = [(xs, ys, zs) for xs in _t3d._window_starts(ww, px, stride_xy) for ys in _t3d._window_starts(hh, py, stride_xy)
+              for zs in _t3d._window_starts(dd, pz, stride_z)]
+    was_training = net.training
+    net.eval()
+    for s0 in range(0, len(starts), batch):
+        grp = starts[s0:s0 + batch]
+        patches = torch.stack([vol[xs:xs + px, ys:ys + py, zs:zs + pz] for xs, ys, zs in grp]).unsqueeze(1)
+        y1 = net(patches)
+        if isinstance(y1, (tuple, list)):
+            y1 = y1[0]
+        assert int(y1.shape[1]) == C, (y1.shape, C)
+        y = _glue.softmax(y1)                                    # [n, C, px, py, pz] planes
+        for i, (xs, ys, zs) in enumerate(grp):
+            _L.call("arco_window_accumulate", _L.ptr(y[i]), C, px, py, pz, _L.ptr(score), _L.ptr(cnt), ww, hh, dd, xs, ys, zs)
+    if was_training:
+        net.train()
+    label = torch.empty((ww, hh, dd), dtype=torch.int64, device=device)
+    _L.call("arco_score_finalize", _L.ptr(score), _L.ptr(cnt), C, ww * hh * dd, _L.ptr(label))
+    if add_pad:
+        (wl, _), (hl, _), (dl, _) = pads
+        label = label[wl:wl + w, hl:hl + h, dl:dl + d].contiguous()
+    return label
+
+
+def _metric_percase_3d_device(pred, gt):
+    """calculate_metric_percase_3d(surface="gpu") for two label tensors on the device; (0, 0, 0, 0) for an all-background prediction
+    (test_util.py:57-58).  The host receives the overlap counts and the non-empty histogram bins, no volume.  (One mask `!= 0` serves
+    both: labels are class indices >= 0, for which metrics.binary's `astype(bool)` and pair_metrics' `> 0` are the same.)"""
+    p, g = (pred != 0).to(torch.int64), (gt != 0).to(torch.int64)
+    n_pred, n_gt, n_both = _t2d.overlap_counts(p, g, 2)[1].cpu().tolist()
+    if n_pred == 0:
+        return (0, 0, 0, 0)
+    dice = 2.0 * n_both / float(n_pred + n_gt)                                   # metrics.binary.dc / jc on the counts
+    jc = float(n_both) / float(n_pred + n_gt - n_both)
+    return (dice, jc) + _surface_gpu.pair_metrics(p, g)
+
+
 def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, preproc_fn=None,
-                  metric_detail=0, nms=0, device="cuda:0", surface="host"):
-    """test_util.test_all_case: the mean (dice, jc, hd95, asd) over `cases` (an all-background prediction scores (0, 0, 0, 0))."""
-    if _surface_gpu.check_route(surface) == "host":
+                  metric_detail=0, nms=0, device="cuda:0", surface="host", cc="host"):
+    """test_util.test_all_case: the mean (dice, jc, hd95, asd) over `cases` (an all-background prediction scores (0, 0, 0, 0)).
+    cc="host" (default) takes the largest component of `nms` from test_util.getLargestCC on the host; cc="gpu" (with surface="gpu"
+    only) is the device-resident tail: the label map of predict_case stays a device tensor, goes through cc_gpu.largest_cc with `nms`,
+    and dice / jc / hd95 / asd come from the overlap-count and surface-distance kernels on it - no volume and no score map reach the
+    host.  Like getLargestCC, cc_gpu.largest_cc takes every non-zero label as one foreground (skimage.measure.label, which the
+    reference calls, joins only voxels of the same value): equal for the two-class case `nms` is used on, not for more classes."""
+    _surface_gpu.check_route(surface)
+    if _cc_gpu.check_cc(cc) == "gpu" and surface != "gpu":
+        raise ValueError('cc="gpu" is the device-resident tail of surface="gpu"; got surface=%r' % (surface,))
+    if surface == "host":
         return _t3d.test_all_case(model, cases, num_classes, patch_size=patch_size, stride_xy=stride_xy, stride_z=stride_z,
                                   preproc_fn=preproc_fn, metric_detail=metric_detail, nms=nms, device=device)
     total, n = np.zeros(4), 0
     for ith, (image, label) in enumerate(cases):
         if preproc_fn is not None:
             image = preproc_fn(image)
-        prediction, _ = _t3d.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, device=device)
-        if nms:
-            prediction = _t3d.getLargestCC(prediction)
-        single = (0, 0, 0, 0) if np.sum(prediction) == 0 else calculate_metric_percase_3d(prediction, np.asarray(label), surface)
+        if cc == "gpu":
+            prediction = predict_case(model, image, stride_xy, stride_z, patch_size, num_classes, device=device)
+            if nms:
+                prediction = _cc_gpu.largest_cc(prediction)
+            single = _metric_percase_3d_device(prediction, torch.from_numpy(np.asarray(label) != 0).to(prediction.device))
+        else:
+            prediction, _ = _t3d.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, device=device)
+            if nms:
+                prediction = _t3d.getLargestCC(prediction)
+            single = (0, 0, 0, 0) if np.sum(prediction) == 0 else calculate_metric_percase_3d(prediction, np.asarray(label), surface)
         if metric_detail:
             print('%02d,\t%.5f, %.5f, %.5f, %.5f' % (ith, *single))
         total += np.asarray(single, dtype=np.float64)

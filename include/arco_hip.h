@@ -464,6 +464,19 @@ int arco_overlap_counts(const int64_t* pred, const int64_t* gt, long n, int C, i
 long arco_surface_ws_bytes(int D, int H, int W, int nc);
 int arco_surface_hist(const int64_t* pred, const int64_t* gt, int D, int H, int W, int ndim, int c_lo, int c_hi, void* ws,
                       long ws_bytes, int64_t* hist, long hist_bytes, void* stream);
+/* ---- V  connected components and the largest one (test_util.py:11-15 getLargestCC) of one contiguous integer label volume [D][H][W]:
+ *      foreground = x != 0; neighbours differ by +-1 in at most `connectivity` axes (scipy's generate_binary_structure(ndim, connectivity);
+ *      1 = faces, ndim = 8 neighbours in 2-D / 26 in 3-D, which is what getLargestCC uses).  ndim 2: D must be 1.
+ *        labels[v]  int32: 0 on background, else 1 + the smallest linear index of v's component;
+ *        largest[v] uint8: 1 on the component with the most voxels (of several that large: the one whose first voxel comes first);
+ *        info       int64[3] = {components, linear index of the winner's first voxel, its voxel count}; {0, -1, 0} without foreground.
+ *      Integer arithmetic and order-independent: identical bits on every run.  ws: arco_cc_ws_bytes(D, H, W) bytes, 8-byte aligned (-1
+ *      for sizes the launch rejects).  ARCO_ERR_ARG before anything is launched or written for: a null pointer, a dim < 1 or > 4096,
+ *      D*H*W >= 2^31, ndim not 2 or 3, ndim 2 with D != 1, connectivity outside 1..ndim, ws_bytes, labels_bytes (4 per voxel),
+ *      largest_bytes (1 per voxel) or info_bytes (24) too small.                                                                  */
+long arco_cc_ws_bytes(int D, int H, int W);
+int arco_cc_largest(const int64_t* x, int D, int H, int W, int ndim, int connectivity, void* ws, long ws_bytes, int32_t* labels,
+                    long labels_bytes, uint8_t* largest, long largest_bytes, int64_t* info, long info_bytes, void* stream);
 /* ---- A  mixing strategies of the unlabeled stream (augment.py:284-313 generate_unsup_data, masks :230-252; volumes
  *      augment_3d.py:182-257).  desc_host[B][8] = {y0, y1, x0, x1, z0, z1, sel_lo, sel_hi} in HOST memory (the host
  *      draws it; it travels in the kernel arguments); Z = 1 in 2-D; mode 0 cutmix, 1 cutout, 2 classmix; data NC[spatial] */
