@@ -155,14 +155,20 @@ def generate_unsup_data_3d(data, target, logits, mode='cutout', desc=None):
 # probability 0.5 each when apply_augmentation, then AdvMorph on the whole batch with probability 0.5
 # ---------------------------------------------------------------------------------------------------------------------
 def _gaussian_blur_radius(sigma, passes=3):
-    """Pillow's _gaussian_blur_radius (BoxBlur.c): fractional box radius of the 3-pass box approximation of a Gaussian."""
+    """Pillow's _gaussian_blur_radius (BoxBlur.c): fractional box radius of the 3-pass box approximation of a Gaussian.
+    Operation by operation: `radius, sigma2, L, l, a` are C floats, so every float operation rounds to float32; the two
+    expressions with a double literal (12.0 * sigma2 + 1.0 under the sqrt, (L - 1.0) / 2.0 under the floor) are double and
+    round at the assignment.  (The whole formula in double, rounded once, is one ulp off for a third of all sigmas, and on a
+    few of them - 0.3, 0.7, 1.3 - the 24-bit box weight moves and pixels differ from Pillow by one level.)"""
     import math
-    sigma2 = float(np.float32(sigma)) * float(np.float32(sigma)) / passes
-    Lb = math.sqrt(12.0 * sigma2 + 1.0)
-    l = math.floor((Lb - 1.0) / 2.0)
-    a = (2 * l + 1) * (l * (l + 1) - 3 * sigma2)
-    a /= 6 * (sigma2 - (l + 1) * (l + 1))
-    return float(np.float32(l + a))
+    f = np.float32
+    r = f(sigma)
+    sigma2 = (r * r) / f(passes)
+    Lb = f(math.sqrt(12.0 * float(sigma2) + 1.0))
+    l = f(math.floor((float(Lb) - 1.0) / 2.0))
+    a = (f(2) * l + f(1)) * (l * (l + f(1)) - f(3) * sigma2)
+    a = a / (f(6) * (sigma2 - (l + f(1)) * (l + f(1))))
+    return float(l + a)
 
 
 def draw_batch_transform_params(n_images, apply_augmentation, scale_size=(1.0, 1.0)):

@@ -578,7 +578,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restri
     const f32x4 v11 = *reinterpret_cast<const f32x4*>(b + ((long)y1 * Wi + x1) * ldx);
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
+    for (int e = 0; e < 4; ++e) o[e] = bl_blend1(v00[e], v01[e], v10[e], v11[e], hx, lx, hy, ly);
     *reinterpret_cast<f32x4*>(Y + (((n * Ho) + yo) * Wo + xo) * ldy + c) = o;
   }
 }
@@ -651,7 +651,7 @@ __global__ __launch_bounds__(256) void gather_upcat_rows_kernel(const float* __r
     const f32x4 v10 = *reinterpret_cast<const f32x4*>(r10 + c), v11 = *reinterpret_cast<const f32x4*>(r11 + c);
     f32x4 r;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
+    for (int e = 0; e < 4; ++e) r[e] = bl_blend1(v00[e], v01[e], v10[e], v11[e], hx, lx, hy, ly);
     *reinterpret_cast<f32x4*>(o + c) = r;
   }
   const TH* h = hi + p * ldhi;
@@ -719,7 +719,7 @@ __global__ __launch_bounds__(256) void lerp4_cat_rows_kernel(const float* __rest
     const f32x4 v10 = *reinterpret_cast<const f32x4*>(v0 + 2 * ldv + c), v11 = *reinterpret_cast<const f32x4*>(v0 + 3 * ldv + c);
     f32x4 r;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = hy * (hx * v00[e] + lx * v01[e]) + ly * (hx * v10[e] + lx * v11[e]);
+    for (int e = 0; e < 4; ++e) r[e] = bl_blend1(v00[e], v01[e], v10[e], v11[e], hx, lx, hy, ly);
     *reinterpret_cast<f32x4*>(o + c) = r;
   }
   const TH* h = hi + pix[j] * ldhi;
@@ -1390,8 +1390,10 @@ int arco_bilinear_bwd(const float* dY, long ldy, int NB, int Hi, int Wi, int C, 
 
 int arco_gather_upcat_rows(const float* lo, long ldlo, int Clo, int Hi, int Wi, const float* hi, long ldhi, int Chi,
                            int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldlo & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && (Clo & 3) == 0 && (Chi & 3) == 0 && (ldlo & 3) == 0 &&
+                 (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && X && (Clo == 0 || (lo && ew_al16(lo))) && (Chi == 0 || (hi && ew_al16(hi))) && ew_al16(X));
   hipLaunchKernelGGL(gather_upcat_rows_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), lo, ldlo, Clo, Hi, Wi,
                      hi, ldhi, Chi, Ho, Wo, pix, n, X, ldx);
   return arco_launch_status();
@@ -1399,8 +1401,10 @@ int arco_gather_upcat_rows(const float* lo, long ldlo, int Clo, int Hi, int Wi, 
 // ... with the map `hi` stored as f16 (f16 activation storage of the U-Net, --fm_rows f16); lo, X fp32.  ldhi in f16 elements.
 int arco_gather_upcat_rows_h(const float* lo, long ldlo, int Clo, int Hi, int Wi, const void* hi, long ldhi, int Chi,
                              int Ho, int Wo, const int64_t* pix, long n, float* X, long ldx, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldlo & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && (Clo & 3) == 0 && (Chi & 3) == 0 && (ldlo & 3) == 0 &&
+                 (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && X && (Clo == 0 || (lo && ew_al16(lo))) && (Chi == 0 || (hi && ew_al8(hi))) && ew_al16(X));
   hipLaunchKernelGGL(gather_upcat_rows_kernel<_Float16>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), lo, ldlo, Clo, Hi, Wi,
                      reinterpret_cast<const _Float16*>(hi), ldhi, Chi, Ho, Wo, pix, n, X, ldx);
   return arco_launch_status();
@@ -1424,16 +1428,18 @@ int arco_up_neighbors(const int64_t* pix, long n, int Hi, int Wi, int Ho, int Wo
 }
 int arco_lerp4_cat_rows(const float* V, long ldv, int Clo, const float* lylx, const float* hi, long ldhi, int Chi,
                         const int64_t* pix, long n, float* X, long ldx, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && (Clo & 3) == 0 && (Chi & 3) == 0 && (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && X && lylx && (Clo == 0 || (V && ew_al16(V))) && (Chi == 0 || (hi && ew_al16(hi))) && ew_al16(X));
   hipLaunchKernelGGL(lerp4_cat_rows_kernel<float>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), V, ldv, Clo, lylx, hi, ldhi,
                      Chi, pix, n, X, ldx);
   return arco_launch_status();
 }
 int arco_lerp4_cat_rows_h(const float* V, long ldv, int Clo, const float* lylx, const void* hi, long ldhi, int Chi,
                           const int64_t* pix, long n, float* X, long ldx, void* stream) {
-  ARCO_CHECK_ARG((Clo & 3) == 0 && (Chi & 3) == 0 && (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
+  ARCO_CHECK_ARG(n >= 0 && Clo >= 0 && Chi >= 0 && (Clo & 3) == 0 && (Chi & 3) == 0 && (ldv & 3) == 0 && (ldhi & 3) == 0 && (ldx & 3) == 0);
   if (n == 0) return ARCO_OK;
+  ARCO_CHECK_ARG(pix && X && lylx && (Clo == 0 || (V && ew_al16(V))) && (Chi == 0 || (hi && ew_al8(hi))) && ew_al16(X));
   hipLaunchKernelGGL(lerp4_cat_rows_kernel<_Float16>, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), V, ldv, Clo, lylx,
                      reinterpret_cast<const _Float16*>(hi), ldhi, Chi, pix, n, X, ldx);
   return arco_launch_status();
@@ -1548,19 +1554,19 @@ int arco_scatter_upcat_rows3d(const float* dX, long ldx, const int64_t* pix, lon
 }
 
 int arco_zero_rows(float* dst, long ld, int C, const int64_t* idx, long n, void* stream) {
-  ARCO_CHECK_ARG(dst && idx && (C & 3) == 0 && (ld & 3) == 0);
+  ARCO_CHECK_ARG(dst && idx && n >= 0 && C > 0 && (C & 3) == 0 && (ld & 3) == 0 && ew_al16(dst));
   if (n == 0) return ARCO_OK;
   hipLaunchKernelGGL(zero_rows_kernel<float>, dim3(ew_grid(n * (C / 4))), dim3(256), 0, as_stream(stream), dst, ld, C, idx, n);
   return arco_launch_status();
 }
 int arco_zero_rows_h(void* dst, long ld, int C, const int64_t* idx, long n, void* stream) {
-  ARCO_CHECK_ARG(dst && idx && (C & 3) == 0 && (ld & 3) == 0);
+  ARCO_CHECK_ARG(dst && idx && n >= 0 && C > 0 && (C & 3) == 0 && (ld & 3) == 0 && ew_al8(dst));
   if (n == 0) return ARCO_OK;
   hipLaunchKernelGGL(zero_rows_kernel<_Float16>, dim3(ew_grid(n * (C / 4))), dim3(256), 0, as_stream(stream), reinterpret_cast<_Float16*>(dst), ld, C, idx, n);
   return arco_launch_status();
 }
 int arco_cast_rows_f2h(const float* src, long ld_src, int C, const int64_t* idx, long n, float scale, void* dst, long ld_dst, void* stream) {
-  ARCO_CHECK_ARG(src && dst && idx && (C & 3) == 0 && (ld_src & 3) == 0 && (ld_dst & 3) == 0);
+  ARCO_CHECK_ARG(src && dst && idx && n >= 0 && C > 0 && (C & 3) == 0 && (ld_src & 3) == 0 && (ld_dst & 3) == 0 && ew_al16(src) && ew_al8(dst));
   if (n == 0) return ARCO_OK;
   hipLaunchKernelGGL(cast_rows_f2h_kernel, dim3(ew_grid(n * (C / 4))), dim3(256), 0, as_stream(stream), src, ld_src, C, idx, n, scale,
                      reinterpret_cast<_Float16*>(dst), ld_dst);

@@ -83,6 +83,18 @@ __device__ __forceinline__ float tl_blend1(float v000, float v001, float v010, f
   return __builtin_fmaf(lz, b1, hz * b0);
 }
 
+// ... and the 4-corner bilinear blend of the 2-D kernels (the dense resize, the row gather and the 4-way lerp of the row-sparse 2-D
+// heads), for the same reason: as the plain expression `hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11)` the three kernels
+// compiled to three different chains (which product of a sum is fused differed per kernel and, in the dense kernel, per element of
+// the f32x4; (1 - l) * v became fma(-l, v, v) in some), and the gather's rows differed from the dense resize in the last bit on
+// 0.5 % of the elements, the lerp's from the gather's on 14 %.  Contraction is off inside, so that the two plain products stay
+// products.
+__device__ __forceinline__ float bl_blend1(float v00, float v01, float v10, float v11, float hx, float lx, float hy, float ly) {
+#pragma clang fp contract(off)
+  const float a0 = __builtin_fmaf(lx, v01, hx * v00), a1 = __builtin_fmaf(lx, v11, hx * v10);
+  return __builtin_fmaf(ly, a1, hy * a0);
+}
+
 // align_corners source index / weight (torch upsample index math in fp32; shared by the resize kernels and the fused epilogue)
 // (contraction off: `src - i0` must subtract from the ROUNDED product, as torch's CPU kernel does - left to -ffp-contract=fast the
 //  compiler fused it into fma(scale, o, -i0) in some kernels and not in others: interpolation weights one ulp apart)

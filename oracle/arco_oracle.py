@@ -827,14 +827,20 @@ def color_jitter_u8(a, order, factors):
 
 
 def gaussian_blur_radius(sigma, passes=3):
-    """Pillow's _gaussian_blur_radius: fractional box radius of the 3-pass box approximation."""
+    """Pillow's _gaussian_blur_radius (BoxBlur.c): fractional box radius of the 3-pass box approximation.  `float sigma2, L, l, a`:
+    each C operation on floats is rounded to float32 (_r32 after every one); `12.0 * sigma2 + 1.0` and `(L - 1.0) / 2.0` are
+    double because of their literals and are rounded when assigned.  Pinned against Pillow by tests/golden/g20_blur_sigmas.npz."""
     import math
-    sigma2 = float(np.float32(sigma)) * float(np.float32(sigma)) / passes
-    L = math.sqrt(12.0 * sigma2 + 1.0)
-    l = math.floor((L - 1.0) / 2.0)
-    a = (2 * l + 1) * (l * (l + 1) - 3 * sigma2)
-    a /= 6 * (sigma2 - (l + 1) * (l + 1))
-    return float(np.float32(l + a))
+    import struct
+    _r32 = lambda v: struct.unpack("<f", struct.pack("<f", v))[0]          # a python float (double) rounded to the nearest float32
+    radius = _r32(sigma)
+    sigma2 = _r32(_r32(radius * radius) / passes)
+    L = _r32(math.sqrt(12.0 * sigma2 + 1.0))
+    l = _r32(math.floor((L - 1.0) / 2.0))
+    a = _r32(_r32(_r32(2 * l) + 1) * _r32(_r32(l * _r32(l + 1)) - _r32(3 * sigma2)))
+    lp = _r32(l + 1)
+    a = _r32(a / _r32(6 * _r32(sigma2 - _r32(lp * lp))))
+    return _r32(l + a)
 
 
 def _box_pass(x, fr):

@@ -712,6 +712,23 @@ def gen_jitter():
     print("g12_jitter", len(out))
 
 
+# ---------------------------------------------------------------- G20 GaussianBlur over sigmas
+def gen_blur_sigmas():
+    """Pillow's own ImageFilter.GaussianBlur of one fixed 48 x 48 'L' and one 24 x 24 'RGB' image (fx.blur_image) at fx.BLUR_SIGMAS:
+    the sigmas where the box radius is sensitive to how _gaussian_blur_radius rounds, the ends of the trainer's range and one
+    sigma per integer box-radius class.  The sigmas are stored as float64."""
+    from PIL import Image, ImageFilter
+    out = {"sigmas": np.array(fx.BLUR_SIGMAS, dtype=np.float64)}
+    for tag in fx.BLUR_IMAGES:
+        a = fx.blur_image(tag)
+        img = Image.fromarray(a[0], 'L') if a.shape[0] == 1 else Image.fromarray(np.ascontiguousarray(a.transpose(1, 2, 0)), 'RGB')
+        for k, sigma in enumerate(fx.BLUR_SIGMAS):
+            arr = np.array(img.filter(ImageFilter.GaussianBlur(radius=float(sigma))))
+            out[f"{tag}_{k}"] = arr[None] if a.shape[0] == 1 else np.ascontiguousarray(arr.transpose(2, 0, 1))
+    np.savez_compressed(os.path.join(OUT, "g20_blur_sigmas.npz"), **out)
+    print("g20_blur_sigmas", len(out))
+
+
 # ---------------------------------------------------------------- G11 2-D evaluation (SURVEY 8f row 3)
 def gen_eval2d(mods):
     """test_2D.test_single_volume (test_2D.py:67-103) pulled out of the source text (the module imports medpy / h5py /
@@ -1295,7 +1312,7 @@ def gen_trainer_loop(mods):
 
 if __name__ == "__main__":
     mods = ref_shim.load()
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "g16", "g17", "g18", "g19", "g20"]
     if "g1" in which: gen_samplers(mods)
     if "g2" in which: gen_loss(mods)
     if "g3" in which: gen_nets(mods)
@@ -1315,3 +1332,4 @@ if __name__ == "__main__":
     if "g17" in which: gen_vnet_norms(mods)
     if "g18" in which: gen_vnet_strict(mods)
     if "g19" in which: gen_trainer_loop(mods)
+    if "g20" in which: gen_blur_sigmas()

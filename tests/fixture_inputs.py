@@ -344,6 +344,25 @@ def jitter_image(seed, C, H, W):
     return x
 
 
+# ---- Pillow's GaussianBlur over sigmas (oracle/gen_golden.py g20, tests/test_augment_kernels_*.py).  The first six are sigmas at which
+# _gaussian_blur_radius evaluated in double and rounded once (instead of in float, operation by operation, as BoxBlur.c does) gives a
+# box radius one ulp off AND a blurred pixel one level off; then the ends of the trainer's range, then one sigma per integer
+# box-radius class 0, 1, 2 (l = floor((sqrt(4 sigma^2 + 1) - 1) / 2)).
+BLUR_SIGMAS = (0.3, 0.7, 1.249, 1.3, 1.129590174359425, 1.1107973060206446, 0.15, 1.15, 0.5, 2.0, 3.0)
+BLUR_IMAGES = {"l": (1, 48, 48), "rgb": (3, 24, 24)}
+
+
+def blur_image(tag):
+    """uint8 [C, H, W]: random levels, a 0 / 255 step edge along the top rows and a constant corner block"""
+    C, H, W = BLUR_IMAGES[tag]
+    rs = np.random.RandomState(8100 + C)
+    a = rs.randint(0, 256, size=(C, H, W)).astype(np.uint8)
+    a[:, :3, :W // 2] = 0
+    a[:, :3, W // 2:] = 255
+    a[:, H - 5:, W - 5:] = 77
+    return a
+
+
 # ---- stage-1 pre-training (oracle/gen_golden.py g13, tests/test_pretrain_*.py): a small ISD configuration
 STAGE1_CFG = dict(K=12, Ts=0.1, Tt=0.1, num_classes=4, latent_pooling_size=1, latent_feature_size=32, output_pooling_size=4,
                   patch_size=16, b=4, labeled_bs=2, size=(64, 64), lr=0.01, steps=2)

@@ -327,6 +327,31 @@ def test_argument_checks_reject_on_the_host():
     spoil("arco_scatter_upcat_rows", [p, 8, p, 1, p, 4, 4, 2, 2, p, 4, 4, 3, 3], nulls(0, 2, 4, 9) + zeros(7, 8, 12, 13) + [(3, -1), (6, -1), (11, -1)])
     # up_neighbors: pix, n, Hi, Wi, Ho, Wo, nb4, lylx
     spoil("arco_up_neighbors", [p, 1, 2, 2, 3, 3, p, p], nulls(0, 6, 7) + zeros(2, 3, 4, 5) + [(1, -1)])
+    # gather_upcat_rows(_h): lo, ldlo, Clo, Hi, Wi, hi, ldhi, Chi, Ho, Wo, pix, n, X, ldx
+    ok = [p, 4, 4, 2, 2, p, 4, 4, 3, 3, p, 1, p, 8]
+    common = nulls(0, 5, 10, 12) + zeros(3, 4, 8, 9) + [(11, -1), (2, 6), (7, 6), (1, 6), (6, 6), (13, 6), (2, -4), (7, -4)]
+    spoil("arco_gather_upcat_rows", ok, common + odd(odd8, 0, 5, 12))
+    spoil("arco_gather_upcat_rows_h", ok, common + odd(odd8, 0, 12) + odd(odd4, 5))
+    for name in ("arco_gather_upcat_rows", "arco_gather_upcat_rows_h"):
+        assert L.query(name, *[None if k in (0, 5, 10, 12) else v for k, v in enumerate(ok[:11])], 0, None, 8, None) == 0      # n == 0: nothing to do
+        assert L.query(name, None, 0, 0, 2, 2, odd4, 4, 4, 3, 3, p, 1, p, 8, None) == bad                                       # an empty lo part: hi is still checked
+    # lerp4_cat_rows(_h): V, ldv, Clo, lylx, hi, ldhi, Chi, pix, n, X, ldx
+    ok = [p, 4, 4, p, p, 4, 4, p, 1, p, 8]
+    common = nulls(0, 3, 4, 7, 9) + [(8, -1), (2, 6), (6, 6), (1, 6), (5, 6), (10, 6), (2, -4), (6, -4)]
+    spoil("arco_lerp4_cat_rows", ok, common + odd(odd8, 0, 4, 9))
+    spoil("arco_lerp4_cat_rows_h", ok, common + odd(odd8, 0, 9) + odd(odd4, 4))
+    for name in ("arco_lerp4_cat_rows", "arco_lerp4_cat_rows_h"):
+        assert L.query(name, None, 4, 4, None, None, 4, 4, None, 0, None, 8, None) == 0                                         # n == 0: nothing to do
+    # zero_rows(_h): dst, ld, C, idx, n;  cast_rows_f2h: src, ld_src, C, idx, n, scale, dst, ld_dst
+    spoil("arco_zero_rows", [p, 4, 4, p, 1], nulls(0, 3) + odd(odd8, 0) + [(2, 6), (2, 0), (2, -4), (1, 6), (4, -1)])
+    spoil("arco_zero_rows_h", [p, 4, 4, p, 1], nulls(0, 3) + odd(odd4, 0) + [(2, 6), (2, 0), (2, -4), (1, 6), (4, -1)])
+    spoil("arco_cast_rows_f2h", [p, 4, 4, p, 1, 1.0, p, 4], nulls(0, 3, 6) + odd(odd8, 0) + odd(odd4, 6) + [(2, 6), (2, 0), (1, 6), (7, 6), (4, -1)])
+    # fold_residual: W, n, c, lo, hi;  unfold_residual: dlo, dhi, n, c, dW (either block may be null);  combine_terms: terms, weights,
+    # n, out;  combine_terms_bwd: weights, n, g, grads
+    spoil("arco_fold_residual", [p, 3, 1, p, p], nulls(0, 3, 4) + [(1, 0), (2, 0), (2, 3), (1, -3), (2, -1)])
+    spoil("arco_unfold_residual", [p, p, 3, 1, p], nulls(4) + [(2, 0), (3, 0), (3, 3), (3, -1)])
+    spoil("arco_combine_terms", [p, p, 2, p], nulls(0, 1, 3) + [(2, 0), (2, 9), (2, -1)])
+    spoil("arco_combine_terms_bwd", [p, 2, p, p], nulls(0, 2, 3) + [(1, 0), (1, 9), (1, -1)])
     # lerp4_cat_rows_bwd: dX, ldx, Clo, lylx, pix, n, dV, ldv, dhi, ldhi, Chi
     spoil("arco_lerp4_cat_rows_bwd", [p, 8, 4, p, p, 1, p, 4, p, 4, 4], nulls(0, 3, 4, 6, 8) + odd(odd8, 0, 6) + [(5, -1), (2, 6), (1, 6), (7, 6), (10, -1)])
     # copy_rows: X, ldx, M, C, Y, ldy, accumulate
