@@ -7,7 +7,11 @@ the reference asks medpy for).  Any other value is a ValueError, raised before a
   3-D (test_util.py:39-79,214) calculate_metric_percase_3d, test_all_case, predict_case
 test_all_case also takes `cc="host"` (default: getLargestCC on the host for `nms`) or `cc="gpu"` (with surface="gpu" only: the label map
 stays on the device from the arg-max through the largest component, utils/cc_gpu.py, to the four metrics).
-Inference, the zoom round trip, the sliding window, the overlap counts and the empty-set conventions are those modules' own."""
+predict_volume and test_single_volume take `zoom="host"` (default: test_2D.predict_volume, scipy's zoom(order=0) on the host twice per
+slice) or `zoom="gpu"` (utils/zoom_gpu.py: the volume is uploaded once, resampled to the patch on the device, and the arg-max map is
+resampled back by the kernel that takes the arg-max - the same label map, bit for bit, as a device tensor; in test_single_volume with
+surface="gpu" only, where it goes on to the overlap counts and the surface kernels without leaving the device).
+Inference, the sliding window, the overlap counts and the empty-set conventions are those modules' own."""
 import numpy as np
 import torch
 
@@ -17,6 +21,7 @@ from . import test_2D as _t2d
 from . import test_util as _t3d
 from .utils import cc_gpu as _cc_gpu
 from .utils import surface_gpu as _surface_gpu
+from .utils import zoom_gpu as _zoom_gpu
 from .utils.metrics import binary as _binary
 
 
@@ -35,13 +40,50 @@ def calculate_metric_percase_2d(pred, gt, surface="host"):
 
 
 @torch.no_grad()
-def test_single_volume(image, label, net, classes, patch_size=(256, 256), device="cuda:0", surface="host"):
+def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0", zoom="host"):
+    """Label map of a [S, X, Y] volume.  zoom="host": test_2D.predict_volume, an int64 numpy array.  zoom="gpu": the same label map as an
+    int64 tensor ON THE DEVICE - the volume is uploaded once as float32 (nearest sampling and zero fill commute with the cast),
+    zoom_gpu.zoom_nearest takes every slice to the patch, the eval-mode net runs in the same batches, and zoom_gpu.argmax_zoom_back
+    turns each batch of logits into labels of the slices' own size.  ValueError, before any launch, when scipy's round trip would not
+    come back to (X, Y) (the host route fails on its assignment there)."""
+    if _zoom_gpu.check_zoom(zoom) == "host":
+        return _t2d.predict_volume(image, net, patch_size, batch=batch, device=device)
+    image = np.asarray(image)
+    S, x, y = image.shape
+    Z0, Z1 = (_zoom_gpu.zoomed_size(n, p)[0] for n, p in zip((x, y), patch_size))      # scipy's int(round(n * (p / n)))
+    back = tuple(int(round(Z * (n / p))) for Z, n, p in zip((Z0, Z1), (x, y), patch_size))
+    if min(x, y) < 2:
+        raise ValueError(f"zoom=\"gpu\": a slice axis of one point is not supported, got slices of {(x, y)}")
+    if back != (x, y):
+        raise ValueError(f"zoom(order=0) of a {(Z0, Z1)} map by {(x / patch_size[0], y / patch_size[1])} has shape {back}, not {(x, y)}")
+    vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
+    zoomed = _zoom_gpu.zoom_nearest(vol, (Z0, Z1))
+    prediction = torch.empty((S, x, y), dtype=torch.int64, device=vol.device)
+    was_training = net.training
+    net.eval()
+    for s0 in range(0, S, batch):
+        logits = net(zoomed[s0:s0 + batch].unsqueeze(1))[0]
+        prediction[s0:s0 + batch] = _zoom_gpu.argmax_zoom_back(logits, (x, y))
+    if was_training:
+        net.train()
+    return prediction
+
+
+@torch.no_grad()
+def test_single_volume(image, label, net, classes, patch_size=(256, 256), device="cuda:0", surface="host", zoom="host"):
     """test_2D.test_single_volume; with surface="gpu" the surface metrics of all classes come from one call on the label volumes that
-    are on the device for the overlap counts already."""
-    if _surface_gpu.check_route(surface) == "host":
+    are on the device for the overlap counts already.  zoom="gpu" (with surface="gpu" only) is the device-resident case: the label map
+    of predict_volume(zoom="gpu") goes to the overlap counts and the surface kernels as the device tensor it is."""
+    _surface_gpu.check_route(surface)
+    if _zoom_gpu.check_zoom(zoom) == "gpu" and surface != "gpu":
+        raise ValueError('zoom="gpu" is the device-resident head of surface="gpu"; got surface=%r' % (surface,))
+    if surface == "host":
         return _t2d.test_single_volume(image, label, net, classes, patch_size, device=device)
-    prediction = _t2d.predict_volume(image, net, patch_size, device=device)
-    pred_d, lab_d = torch.from_numpy(prediction).to(device), torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device)
+    if zoom == "gpu":
+        pred_d = predict_volume(image, net, patch_size, device=device, zoom="gpu")
+    else:
+        pred_d = torch.from_numpy(_t2d.predict_volume(image, net, patch_size, device=device)).to(device)
+    lab_d = torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device)
     cnt = _t2d.overlap_counts(pred_d, lab_d, classes).cpu().numpy()
     scored = _surface_gpu.surface_metrics(pred_d, lab_d, range(1, classes)) if classes > 1 else []
     metric_list = []

@@ -477,6 +477,24 @@ int arco_surface_hist(const int64_t* pred, const int64_t* gt, int D, int H, int 
 long arco_cc_ws_bytes(int D, int H, int W);
 int arco_cc_largest(const int64_t* x, int D, int H, int W, int ndim, int connectivity, void* ws, long ws_bytes, int32_t* labels,
                     long labels_bytes, uint8_t* largest, long largest_bytes, int64_t* info, long info_bytes, void* stream);
+/* ---- V  the zoom(order=0) round trip of 2-D evaluation (test_2D.py:72-88; csrc/zoom.hip, arco_amd/utils/zoom_gpu.py), bit for bit
+ *      scipy.ndimage.zoom(order=0, mode='constant'): output index o of an axis of n_in points resampled to n_out >= 2 points reads input
+ *      index floor(cc + 0.5), cc = (double)o * z, z = (n_in - 1) / (n_out - 1) computed by the caller in float64; the output is the
+ *      constant 0 where !(0 <= cc <= n_in - 1) (for some sizes the last index lands one ulp above n_in - 1: a whole zeroed last row or
+ *      column).  Float64 without contraction; an index depends on o alone, not on the slice.
+ *      arco_zoom_nearest2d: src [S][n0][n1] -> out [S][N0][N1], both contiguous, elements of elem_bytes = 4 or 8 bytes moved as bits (fp32
+ *      images, int64 label maps); z0 / z1 the steps of the two axes.  Any alignment of `out` is taken (16-byte stores where it allows).
+ *      ARCO_ERR_ARG before anything is launched for: a null pointer, S / n0 / n1 < 1, N0 / N1 < 2, elem_bytes not 4 or 8, a z that is
+ *      negative or not finite.
+ *      arco_argmax_zoom_back2d: the fused tail.  X: logits rows [n * P0 * P1][ld] (channels-last, C <= 32 classes, ld >= C) ->
+ *      out int64 [n][N0][N1]: label 0 where the sampled pixel of the P0 x P1 map is outside, else the class arco_softmax_rows returns as
+ *      `amax` for that one row (the first strict maximum of the fp32 probabilities, not the arg-max of the logits).  Rows that no output
+ *      pixel samples are not read.  ARCO_ERR_ARG before anything is launched for: a null pointer, C < 1 or > 32, ld < C, n / P0 / P1
+ *      < 1, N0 / N1 < 2, a z that is negative or not finite.                                                                        */
+int arco_zoom_nearest2d(const void* src, int S, int n0, int n1, int N0, int N1, double z0, double z1, int elem_bytes, void* out,
+                        void* stream);
+int arco_argmax_zoom_back2d(const float* X, long ld, int C, int n, int P0, int P1, int N0, int N1, double z0, double z1, int64_t* out,
+                            void* stream);
 /* ---- A  mixing strategies of the unlabeled stream (augment.py:284-313 generate_unsup_data, masks :230-252; volumes
  *      augment_3d.py:182-257).  desc_host[B][8] = {y0, y1, x0, x1, z0, z1, sel_lo, sel_hi} in HOST memory (the host
  *      draws it; it travels in the kernel arguments); Z = 1 in 2-D; mode 0 cutmix, 1 cutout, 2 classmix; data NC[spatial] */
