@@ -11,6 +11,12 @@ predict_volume and test_single_volume take `zoom="host"` (default: test_2D.predi
 slice) or `zoom="gpu"` (utils/zoom_gpu.py: the volume is uploaded once, resampled to the patch on the device, and the arg-max map is
 resampled back by the kernel that takes the arg-max - the same label map, bit for bit, as a device tensor; in test_single_volume with
 surface="gpu" only, where it goes on to the overlap counts and the surface kernels without leaving the device).
+The metric functions, test_single_volume and test_all_case also take metrics.binary's `voxelspacing=None, connectivity=1` (medpy's
+meaning: None is 1.0, a number is broadcast, a sequence has one entry per axis of the scored map - three for the [S, X, Y] volume of
+test_single_volume; connectivity 1..ndim).  With both at their defaults every function takes the path it took without them.  Otherwise
+surface="host" gives hd95 / asd from metrics.binary with the two arguments on the label map of the same predict functions, and
+surface="gpu" from surface_gpu.spaced_metrics / spaced_pair_metrics (float64 records, csrc/surface_sp.hip) on the device tensors that are
+there already - zoom="gpu" and cc="gpu" included.  A bad spacing or connectivity is a ValueError before any GPU work.
 Inference, the sliding window, the overlap counts and the empty-set conventions are those modules' own."""
 import numpy as np
 import torch
@@ -25,17 +31,41 @@ from .utils import zoom_gpu as _zoom_gpu
 from .utils.metrics import binary as _binary
 
 
-def calculate_metric_percase_2d(pred, gt, surface="host"):
+def _unit(voxelspacing, connectivity):
+    """Both surface arguments at their defaults: the unit-spacing, connectivity-1 paths."""
+    return voxelspacing is None and isinstance(connectivity, int) and connectivity == 1
+
+
+def _shape(x):
+    return tuple(x.shape) if torch.is_tensor(x) else np.shape(x)
+
+
+def calculate_metric_percase_2d(pred, gt, surface="host", voxelspacing=None, connectivity=1):
     """(dice, jc, hd95, asd) of two binary masks (numpy or torch) with test_2D.calculate_metric_percase's conventions."""
-    if _surface_gpu.check_route(surface) == "host":
+    unit = _unit(voxelspacing, connectivity)
+    if _surface_gpu.check_route(surface) == "host" and unit:
         return _t2d.calculate_metric_percase(pred, gt)
+    if not unit:
+        _surface_gpu.check_spaced_args(voxelspacing, connectivity, len(_shape(pred)))
+    if surface == "host":
+        pred = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred) > 0
+        gt = np.asarray(gt.cpu() if torch.is_tensor(gt) else gt) > 0
+        dice, jc = _t2d._dice_jc(int(pred.sum()), int(gt.sum()), int(np.logical_and(pred, gt).sum()))
+        hd95 = asd = 0.0
+        if pred.sum() > 0 and gt.sum() > 0:
+            asd = _binary.asd(pred, gt, voxelspacing, connectivity)
+            hd95 = _binary.hd95(pred, gt, voxelspacing, connectivity)
+        return dice, jc, hd95, asd
     p = (pred if torch.is_tensor(pred) else torch.from_numpy(np.asarray(pred) > 0)) > 0
     g = (gt if torch.is_tensor(gt) else torch.from_numpy(np.asarray(gt) > 0)) > 0
     n_pred, n_gt, n_both = int(p.sum()), int(g.sum()), int((p & g.to(p.device)).sum())
     dice, jc = _t2d._dice_jc(n_pred, n_gt, n_both)
     hd95 = asd = 0.0
     if n_pred > 0 and n_gt > 0:
-        hd95, asd = _surface_gpu.pair_metrics(p, g)
+        if unit:
+            hd95, asd = _surface_gpu.pair_metrics(p, g)
+        else:
+            hd95, asd = _surface_gpu.spaced_pair_metrics(p, g, voxelspacing, connectivity)
     return dice, jc, hd95, asd
 
 
@@ -70,22 +100,45 @@ def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0",
 
 
 @torch.no_grad()
-def test_single_volume(image, label, net, classes, patch_size=(256, 256), device="cuda:0", surface="host", zoom="host"):
+def test_single_volume(image, label, net, classes, patch_size=(256, 256), device="cuda:0", surface="host", zoom="host",
+                       voxelspacing=None, connectivity=1):
     """test_2D.test_single_volume; with surface="gpu" the surface metrics of all classes come from one call on the label volumes that
     are on the device for the overlap counts already.  zoom="gpu" (with surface="gpu" only) is the device-resident case: the label map
-    of predict_volume(zoom="gpu") goes to the overlap counts and the surface kernels as the device tensor it is."""
+    of predict_volume(zoom="gpu") goes to the overlap counts and the surface kernels as the device tensor it is.  Every class is scored on
+    the [S, X, Y] volume as the 3-D object it is, so a voxelspacing has three entries."""
     _surface_gpu.check_route(surface)
     if _zoom_gpu.check_zoom(zoom) == "gpu" and surface != "gpu":
         raise ValueError('zoom="gpu" is the device-resident head of surface="gpu"; got surface=%r' % (surface,))
-    if surface == "host":
+    unit = _unit(voxelspacing, connectivity)
+    if surface == "host" and unit:
         return _t2d.test_single_volume(image, label, net, classes, patch_size, device=device)
+    if not unit:
+        _surface_gpu.check_spaced_args(voxelspacing, connectivity, 3)
+    if surface == "host":
+        prediction = _t2d.predict_volume(image, net, patch_size, device=device)
+        cnt = _t2d.overlap_counts(torch.from_numpy(prediction).to(device), torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device),
+                                  classes).cpu().numpy()
+        metric_list = []
+        for c in range(1, classes):
+            dice, jc = _t2d._dice_jc(int(cnt[c, 0]), int(cnt[c, 1]), int(cnt[c, 2]))
+            hd95 = asd = 0.0
+            if cnt[c, 0] > 0 and cnt[c, 1] > 0:
+                asd = _binary.asd(prediction == c, label == c, voxelspacing, connectivity)
+                hd95 = _binary.hd95(prediction == c, label == c, voxelspacing, connectivity)
+            metric_list.append((dice, jc, hd95, asd))
+        return metric_list
     if zoom == "gpu":
         pred_d = predict_volume(image, net, patch_size, device=device, zoom="gpu")
     else:
         pred_d = torch.from_numpy(_t2d.predict_volume(image, net, patch_size, device=device)).to(device)
     lab_d = torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device)
     cnt = _t2d.overlap_counts(pred_d, lab_d, classes).cpu().numpy()
-    scored = _surface_gpu.surface_metrics(pred_d, lab_d, range(1, classes)) if classes > 1 else []
+    if classes <= 1:
+        scored = []
+    elif unit:
+        scored = _surface_gpu.surface_metrics(pred_d, lab_d, range(1, classes))
+    else:
+        scored = _surface_gpu.spaced_metrics(pred_d, lab_d, range(1, classes), voxelspacing, connectivity)
     metric_list = []
     for c in range(1, classes):
         dice, jc = _t2d._dice_jc(int(cnt[c, 0]), int(cnt[c, 1]), int(cnt[c, 2]))
@@ -96,11 +149,18 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), device
     return metric_list
 
 
-def calculate_metric_percase_3d(pred, gt, surface="host"):
-    """(dice, jc, hd95, asd) as test_util.calculate_metric_percase; with surface="gpu" both surface metrics from one histogram call."""
-    if _surface_gpu.check_route(surface) == "host":
+def calculate_metric_percase_3d(pred, gt, surface="host", voxelspacing=None, connectivity=1):
+    """(dice, jc, hd95, asd) as test_util.calculate_metric_percase; with surface="gpu" both surface metrics from one kernel call."""
+    unit = _unit(voxelspacing, connectivity)
+    if _surface_gpu.check_route(surface) == "host" and unit:
         return _t3d.calculate_metric_percase(pred, gt)
-    return (_binary.dc(pred, gt), _binary.jc(pred, gt)) + _surface_gpu.pair_metrics(pred, gt)
+    if unit:
+        return (_binary.dc(pred, gt), _binary.jc(pred, gt)) + _surface_gpu.pair_metrics(pred, gt)
+    _surface_gpu.check_spaced_args(voxelspacing, connectivity, len(_shape(pred)))
+    if surface == "host":
+        return (_binary.dc(pred, gt), _binary.jc(pred, gt), _binary.hd95(pred, gt, voxelspacing, connectivity),
+                _binary.asd(pred, gt, voxelspacing, connectivity))
+    return (_binary.dc(pred, gt), _binary.jc(pred, gt)) + _surface_gpu.spaced_pair_metrics(pred, gt, voxelspacing, connectivity)
 
 
 @torch.no_grad()
@@ -148,7 +208,7 @@ def predict_case(net, image, stride_xy, stride_z, patch_size, num_classes, batch
     return label
 
 
-def _metric_percase_3d_device(pred, gt):
+def _metric_percase_3d_device(pred, gt, voxelspacing=None, connectivity=1):
     """calculate_metric_percase_3d(surface="gpu") for two label tensors on the device; (0, 0, 0, 0) for an all-background prediction
     (test_util.py:57-58).  The host receives the overlap counts and the non-empty histogram bins, no volume.  (One mask `!= 0` serves
     both: labels are class indices >= 0, for which metrics.binary's `astype(bool)` and pair_metrics' `> 0` are the same.)"""
@@ -158,11 +218,13 @@ def _metric_percase_3d_device(pred, gt):
         return (0, 0, 0, 0)
     dice = 2.0 * n_both / float(n_pred + n_gt)                                   # metrics.binary.dc / jc on the counts
     jc = float(n_both) / float(n_pred + n_gt - n_both)
-    return (dice, jc) + _surface_gpu.pair_metrics(p, g)
+    if _unit(voxelspacing, connectivity):
+        return (dice, jc) + _surface_gpu.pair_metrics(p, g)
+    return (dice, jc) + _surface_gpu.spaced_pair_metrics(p, g, voxelspacing, connectivity)
 
 
 def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, preproc_fn=None,
-                  metric_detail=0, nms=0, device="cuda:0", surface="host", cc="host"):
+                  metric_detail=0, nms=0, device="cuda:0", surface="host", cc="host", voxelspacing=None, connectivity=1):
     """test_util.test_all_case: the mean (dice, jc, hd95, asd) over `cases` (an all-background prediction scores (0, 0, 0, 0)).
     cc="host" (default) takes the largest component of `nms` from test_util.getLargestCC on the host; cc="gpu" (with surface="gpu"
     only) is the device-resident tail: the label map of predict_case stays a device tensor, goes through cc_gpu.largest_cc with `nms`,
@@ -172,9 +234,12 @@ def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_x
     _surface_gpu.check_route(surface)
     if _cc_gpu.check_cc(cc) == "gpu" and surface != "gpu":
         raise ValueError('cc="gpu" is the device-resident tail of surface="gpu"; got surface=%r' % (surface,))
-    if surface == "host":
+    unit = _unit(voxelspacing, connectivity)
+    if surface == "host" and unit:
         return _t3d.test_all_case(model, cases, num_classes, patch_size=patch_size, stride_xy=stride_xy, stride_z=stride_z,
                                   preproc_fn=preproc_fn, metric_detail=metric_detail, nms=nms, device=device)
+    if not unit:
+        _surface_gpu.check_spaced_args(voxelspacing, connectivity, 3)
     total, n = np.zeros(4), 0
     for ith, (image, label) in enumerate(cases):
         if preproc_fn is not None:
@@ -183,12 +248,14 @@ def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_x
             prediction = predict_case(model, image, stride_xy, stride_z, patch_size, num_classes, device=device)
             if nms:
                 prediction = _cc_gpu.largest_cc(prediction)
-            single = _metric_percase_3d_device(prediction, torch.from_numpy(np.asarray(label) != 0).to(prediction.device))
+            single = _metric_percase_3d_device(prediction, torch.from_numpy(np.asarray(label) != 0).to(prediction.device),
+                                               voxelspacing, connectivity)
         else:
             prediction, _ = _t3d.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, device=device)
             if nms:
                 prediction = _t3d.getLargestCC(prediction)
-            single = (0, 0, 0, 0) if np.sum(prediction) == 0 else calculate_metric_percase_3d(prediction, np.asarray(label), surface)
+            single = ((0, 0, 0, 0) if np.sum(prediction) == 0 else
+                      calculate_metric_percase_3d(prediction, np.asarray(label), surface, voxelspacing, connectivity))
         if metric_detail:
             print('%02d,\t%.5f, %.5f, %.5f, %.5f' % (ith, *single))
         total += np.asarray(single, dtype=np.float64)

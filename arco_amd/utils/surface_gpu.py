@@ -8,7 +8,9 @@ computed in integer arithmetic (exact, independent of the order of arrival).  On
 finishes in float64 with numpy's own percentile:
   v = repeat(sqrt(k), count);  hd95 = percentile(v of both directions pooled, 95);  asd = mean(v of direction 0)
 sqrt of the integer k is bit for bit what distance_transform_edt returns at that voxel, so hd95 equals the host route exactly and asd
-up to the order of one float64 sum.  Anisotropic spacing breaks the integer histogram: that stays with the host route (utils/metrics.py)."""
+up to the order of one float64 sum.  Anisotropic spacing breaks the integer histogram: a `voxelspacing` or a `connectivity` other
+than 1 takes the float64 record kernels (csrc/surface_sp.hip) through the `spaced_*` functions at the end of this module, which return
+one squared distance per border voxel; `pair_metrics` / `hd95` / `asd` stay the integer-exact unit-spacing route and refuse both."""
 import numpy as np
 import torch
 
@@ -144,3 +146,129 @@ def hd95(result, reference, voxelspacing=None, connectivity=1, device=None):
 def asd(result, reference, voxelspacing=None, connectivity=1, device=None):
     """metrics.binary.asd on the GPU."""
     return pair_metrics(result, reference, voxelspacing, connectivity, device)[1]
+
+
+# ---- a voxel spacing and a connectivity: float64 records instead of the integer histogram (csrc/surface_sp.hip) ---------------------------
+def _spacing(voxelspacing, ndim):
+    """medpy's voxelspacing for a map of `ndim` axes as a tuple of floats: None is 1.0, a scalar is broadcast, a sequence has one entry
+    per axis."""
+    if voxelspacing is None:
+        return (1.0,) * ndim
+    sp = np.asarray(voxelspacing, dtype=np.float64)
+    if sp.ndim == 0:
+        sp = np.full(ndim, float(sp))
+    if sp.shape != (ndim,):
+        raise ValueError(f"voxelspacing must be None, a number or {ndim} numbers (one per axis), got {voxelspacing!r}")
+    if not (np.isfinite(sp).all() and (sp > 0).all()):
+        raise ValueError(f"every voxelspacing must be finite and greater than 0, got {voxelspacing!r}")
+    return tuple(float(v) for v in sp)
+
+
+def _connectivity(connectivity, ndim):
+    if not isinstance(connectivity, (int, np.integer)) or isinstance(connectivity, bool) or not 1 <= connectivity <= ndim:
+        raise ValueError(f"connectivity must be an integer in 1..{ndim}, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _map_ndim(shape, ndim):
+    if len(shape) not in (2, 3):
+        raise ValueError(f"label maps must be 2-D or 3-D, got shape {tuple(shape)}")
+    ndim = len(shape) if ndim is None else int(ndim)
+    if ndim not in (2, 3) or (ndim == 2 and len(shape) == 3 and shape[0] != 1):
+        raise ValueError(f"ndim must be 2 or 3, and 2 only for a map [H, W] or [1, H, W]; got shape {tuple(shape)} and ndim {ndim}")
+    if min(shape) < 1 or max(shape) > MAX_DIM:
+        raise ValueError(f"every dim must be in 1..{MAX_DIM}, got {tuple(shape)}")
+    return ndim
+
+
+def check_spaced_args(voxelspacing, connectivity, ndim):
+    """ValueError for a voxelspacing or a connectivity that a map of `ndim` axes cannot take; (spacing per axis, connectivity)."""
+    return _spacing(voxelspacing, ndim), _connectivity(connectivity, ndim)
+
+
+def spaced_launch(pred, gt, classes, voxelspacing=None, connectivity=1, ndim=None, cap=None):
+    """One arco_surface_sp_dist call for two integer label tensors on the GPU: (val float64 [cap], tag int32 [cap], count int64 [1]) ON
+    THE DEVICE, not waited for.  Every argument check comes before any GPU work.  cap defaults to 2 * voxels, which cannot overflow."""
+    c_lo, c_hi = _class_range(classes)
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)):
+        raise TypeError("the spaced surface functions take torch tensors on the GPU")
+    if pred.dtype.is_floating_point or gt.dtype.is_floating_point or pred.dtype == torch.bool or gt.dtype == torch.bool:
+        raise TypeError("the spaced surface functions take integer label tensors")
+    if pred.shape != gt.shape:
+        raise ValueError(f"shapes differ: {tuple(pred.shape)} vs {tuple(gt.shape)}")
+    ndim = _map_ndim(tuple(pred.shape), ndim)
+    sp = _spacing(voxelspacing, ndim)
+    conn = _connectivity(connectivity, ndim)
+    cap = 2 * pred.numel() if cap is None else int(cap)
+    if cap < 1:
+        raise ValueError(f"cap must be at least 1, got {cap}")
+    L.require_gpu(pred, gt)
+    D, H, W = (1, *pred.shape) if pred.dim() == 2 else pred.shape
+    sz, sy, sx = (1.0, *sp) if ndim == 2 else sp
+    p = pred.to(torch.int64).contiguous()
+    g = gt.to(torch.int64).contiguous()
+    ws_bytes = L.query("arco_surface_sp_ws_bytes", D, H, W, c_hi - c_lo + 1)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=p.device)
+    val = torch.empty(cap, dtype=torch.float64, device=p.device)
+    tag = torch.empty(cap, dtype=torch.int32, device=p.device)
+    count = torch.empty(1, dtype=torch.int64, device=p.device)
+    with torch.cuda.device(p.device):
+        L.call("arco_surface_sp_dist", L.ptr(p), L.ptr(g), D, H, W, ndim, conn, sz, sy, sx, c_lo, c_hi, L.ptr(ws), ws_bytes,
+               L.ptr(val), L.ptr(tag), cap, L.ptr(count))
+    return val, tag, count
+
+
+def spaced_records(pred, gt, classes, voxelspacing=None, connectivity=1, ndim=None, cap=None):
+    """(val, tag): the records of spaced_launch on the host - float64 SQUARED distances in the order they arrived, and int32 tags
+    (class index * 2 + direction).  Only the first `count` records travel.  RuntimeError when the kernels counted more records than
+    the capacity `cap`."""
+    val, tag, count = spaced_launch(pred, gt, classes, voxelspacing, connectivity, ndim, cap)
+    n = int(count.item())
+    if n > val.numel():
+        raise RuntimeError(f"arco_amd: {n} surface records do not fit the capacity of {val.numel()}")
+    return val[:n].cpu().numpy(), tag[:n].cpu().numpy()
+
+
+def spaced_distances(pred, gt, classes, voxelspacing=None, connectivity=1, ndim=None):
+    """[(d0, d1)] per class: two ascending float64 numpy arrays of surface distances, d0 from border(pred == c) to border(gt == c) and
+    d1 the other way; both empty for a class absent from either map.  The squared records are sorted on the host - which makes the
+    result independent of the order they arrived in - and np.sqrt is taken there."""
+    classes = list(classes)
+    val, tag = spaced_records(pred, gt, classes, voxelspacing, connectivity, ndim)
+    return [tuple(np.sqrt(np.sort(val[tag == 2 * c + d])) for d in (0, 1)) for c in range(len(classes))]
+
+
+def finish_distances(d0, d1):
+    """(hd95, asd) in float64 from the distances of the two directions; None when a direction is empty."""
+    if d0.size == 0 or d1.size == 0:
+        return None
+    return float(np.percentile(np.hstack((d0, d1)), 95)), float(d0.mean())
+
+
+def spaced_metrics(pred, gt, classes, voxelspacing=None, connectivity=1):
+    """[(hd95, asd) or None] per class, as surface_metrics, with metrics.binary's voxelspacing and connectivity."""
+    return [finish_distances(d0, d1) for d0, d1 in spaced_distances(pred, gt, classes, voxelspacing, connectivity)]
+
+
+def spaced_pair_metrics(result, reference, voxelspacing=None, connectivity=1, device=None):
+    """pair_metrics with a voxelspacing (None, a number, or one number per axis) and a connectivity (1..ndim): (hd95, asd) of one pair of
+    binary masks from ONE call.  ValueError for a bad argument before any GPU work; metrics.binary's RuntimeError for an empty mask."""
+    ndim = _map_ndim(tuple(result.shape if torch.is_tensor(result) else np.shape(result)), None)
+    check_spaced_args(voxelspacing, connectivity, ndim)
+    a = _mask(result, device)
+    b = _mask(reference, a.device)
+    got = spaced_metrics(a, b, (1,), voxelspacing, connectivity)[0]
+    if got is None:
+        any_a, any_b = torch.stack((a.any(), b.any())).cpu().tolist()
+        raise RuntimeError(_EMPTY[0] if not any_a else _EMPTY[1])
+    return got
+
+
+def spaced_hd95(result, reference, voxelspacing=None, connectivity=1, device=None):
+    """metrics.binary.hd95 with its voxelspacing and connectivity on the GPU."""
+    return spaced_pair_metrics(result, reference, voxelspacing, connectivity, device)[0]
+
+
+def spaced_asd(result, reference, voxelspacing=None, connectivity=1, device=None):
+    """metrics.binary.asd with its voxelspacing and connectivity on the GPU."""
+    return spaced_pair_metrics(result, reference, voxelspacing, connectivity, device)[1]

@@ -464,6 +464,23 @@ int arco_overlap_counts(const int64_t* pred, const int64_t* gt, long n, int C, i
 long arco_surface_ws_bytes(int D, int H, int W, int nc);
 int arco_surface_hist(const int64_t* pred, const int64_t* gt, int D, int H, int W, int ndim, int c_lo, int c_hi, void* ws,
                       long ws_bytes, int64_t* hist, long hist_bytes, void* stream);
+/* ---- V  the same surface distances with a voxel spacing (sz, sy, sx > 0 and finite; sz is ignored for ndim 2) and a connectivity
+ *      (1..ndim: a neighbour differs by +-1 in 1 to `connectivity` axes, scipy's generate_binary_structure(ndim, connectivity); outside
+ *      the array counts as unset), in float64.  With w_a(e) = fl(fl(s_a * e) * fl(s_a * e)) the squared distance of a voxel v to
+ *      border(B) is the minimum over the voxels u of border(B) of fl(fl(w_x(dx) + w_y(dy)) + w_z(dz)), (dz, dy, dx) = v - u - every
+ *      operation rounded once, none fused, the minimum exact - so an O(n^2) restatement in that order reproduces it bit for bit.
+ *      Every voxel of border(A) with a finite squared distance appends one record: val = that float64, tag = (c - c_lo) * 2 + direction
+ *      (0: A = pred == c, B = gt == c; 1: exchanged).  The records are packed through an integer cursor (no float atomics); their
+ *      order is that of arrival, their multiset is fixed.  count[0] (zeroed here) ends at the true number of records; only the
+ *      first min(count, cap) are written - a voxel is in one class per map, so cap = 2 * D * H * W never overflows.
+ *      ws: arco_surface_sp_ws_bytes(D, H, W, classes) bytes (two float64 planes per class and direction; -1 for sizes the launch
+ *      rejects).  ARCO_ERR_ARG before anything is launched for: a null pointer, a dim < 1 or > 4096, ndim not 2 or 3, ndim 2 with
+ *      D != 1, connectivity outside 1..ndim, a spacing that is not finite and > 0, c_hi < c_lo, more than 32 classes, ws_bytes too
+ *      small, cap < 1.                                                                                                            */
+long arco_surface_sp_ws_bytes(int D, int H, int W, int nc);
+int arco_surface_sp_dist(const int64_t* pred, const int64_t* gt, int D, int H, int W, int ndim, int connectivity, double sz, double sy,
+                         double sx, int c_lo, int c_hi, void* ws, long ws_bytes, double* val, int32_t* tag, long cap, int64_t* count,
+                         void* stream);
 /* ---- V  connected components and the largest one (test_util.py:11-15 getLargestCC) of one contiguous integer label volume [D][H][W]:
  *      foreground = x != 0; neighbours differ by +-1 in at most `connectivity` axes (scipy's generate_binary_structure(ndim, connectivity);
  *      1 = faces, ndim = 8 neighbours in 2-D / 26 in 3-D, which is what getLargestCC uses).  ndim 2: D must be 1.
