@@ -47,6 +47,7 @@ _SIGS = {
     "arco_surface_hist": [_P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P],
     "arco_surface_sp_dist": [_P, _P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _I, _P, _L, _P, _P, _L, _P, _P],
     "arco_cc_largest": [_P, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P],
+    "arco_cc_value_largest": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P],
     "arco_zoom_nearest2d": [_P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _I, _P, _P],
     "arco_argmax_zoom_back2d": [_P, _L, _I, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P],
     "arco_mix_unsup": [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
@@ -186,6 +187,7 @@ _QUERIES = {   # plain host helpers returning sizes
     "arco_surface_ws_bytes": ([_I, _I, _I, _I], _L),
     "arco_surface_sp_ws_bytes": ([_I, _I, _I, _I], _L),
     "arco_cc_ws_bytes": ([_I, _I, _I], _L),
+    "arco_cc_value_ws_bytes": ([_I, _I, _I, _I], _L),
     # host-side native sampler replay (no GPU work)
     "arco_grid_sample": ([_P, _L, _L, _L, _I, _I, _P], _L),
     "arco_randint": ([_P, _L, _L, _L, _P], _L),

@@ -17,6 +17,12 @@ test_single_volume; connectivity 1..ndim).  With both at their defaults every fu
 surface="host" gives hd95 / asd from metrics.binary with the two arguments on the label map of the same predict functions, and
 surface="gpu" from surface_gpu.spaced_metrics / spaced_pair_metrics (float64 records, csrc/surface_sp.hip) on the device tensors that are
 there already - zoom="gpu" and cc="gpu" included.  A bad spacing or connectivity is a ValueError before any GPU work.
+What `nms` keeps: test_all_case takes `nms_mode="foreground"` (default: getLargestCC / largest_cc, every non-zero label one foreground),
+"value" (the reference's own meaning through skimage.measure.label: the largest component of EQUAL values, cc_host.getLargestCC_by_value
+/ cc_gpu.largest_cc_by_value) or "per_class" (the largest component of every class, cc_host.keep_largest_per_class /
+cc_gpu.largest_per_class); the keyword is read only when `nms` is set, any other value is a ValueError before any GPU work.
+test_single_volume takes `nms=0, cc="host"`: nms=1 keeps each class's largest component of the [S, X, Y] prediction (csrc/cc_value.hip on
+cc="gpu", which needs surface="gpu") before the overlap counts and the surface metrics.
 Inference, the sliding window, the overlap counts and the empty-set conventions are those modules' own."""
 import numpy as np
 import torch
@@ -26,6 +32,7 @@ from . import glue as _glue
 from . import test_2D as _t2d
 from . import test_util as _t3d
 from .utils import cc_gpu as _cc_gpu
+from .utils import cc_host as _cc_host
 from .utils import surface_gpu as _surface_gpu
 from .utils import zoom_gpu as _zoom_gpu
 from .utils.metrics import binary as _binary
@@ -34,6 +41,16 @@ from .utils.metrics import binary as _binary
 def _unit(voxelspacing, connectivity):
     """Both surface arguments at their defaults: the unit-spacing, connectivity-1 paths."""
     return voxelspacing is None and isinstance(connectivity, int) and connectivity == 1
+
+
+NMS_MODES = ("foreground", "value", "per_class")
+
+
+def _check_nms_mode(nms_mode):
+    """The `nms_mode=` keyword of test_all_case: what `nms` keeps."""
+    if nms_mode not in NMS_MODES:
+        raise ValueError(f"nms_mode must be one of {NMS_MODES}, got {nms_mode!r}")
+    return nms_mode
 
 
 def _shape(x):
@@ -101,21 +118,28 @@ def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0",
 
 @torch.no_grad()
 def test_single_volume(image, label, net, classes, patch_size=(256, 256), device="cuda:0", surface="host", zoom="host",
-                       voxelspacing=None, connectivity=1):
+                       voxelspacing=None, connectivity=1, nms=0, cc="host"):
     """test_2D.test_single_volume; with surface="gpu" the surface metrics of all classes come from one call on the label volumes that
     are on the device for the overlap counts already.  zoom="gpu" (with surface="gpu" only) is the device-resident case: the label map
     of predict_volume(zoom="gpu") goes to the overlap counts and the surface kernels as the device tensor it is.  Every class is scored on
-    the [S, X, Y] volume as the 3-D object it is, so a voxelspacing has three entries."""
+    the [S, X, Y] volume as the 3-D object it is, so a voxelspacing has three entries.
+    nms=1 keeps, before anything is counted or measured, only the largest component of every class of the [S, X, Y] prediction (the 3-D
+    object it is, full connectivity): cc="host" (default) through cc_host.keep_largest_per_class on the host map, cc="gpu" (with
+    surface="gpu" only) through cc_gpu.largest_per_class - with zoom="gpu" the label map then never leaves the device."""
     _surface_gpu.check_route(surface)
     if _zoom_gpu.check_zoom(zoom) == "gpu" and surface != "gpu":
         raise ValueError('zoom="gpu" is the device-resident head of surface="gpu"; got surface=%r' % (surface,))
+    if _cc_gpu.check_cc(cc) == "gpu" and surface != "gpu":
+        raise ValueError('cc="gpu" is the device-resident tail of surface="gpu"; got surface=%r' % (surface,))
     unit = _unit(voxelspacing, connectivity)
-    if surface == "host" and unit:
+    if surface == "host" and unit and not nms:
         return _t2d.test_single_volume(image, label, net, classes, patch_size, device=device)
     if not unit:
         _surface_gpu.check_spaced_args(voxelspacing, connectivity, 3)
     if surface == "host":
         prediction = _t2d.predict_volume(image, net, patch_size, device=device)
+        if nms:
+            prediction = _cc_host.keep_largest_per_class(prediction)
         cnt = _t2d.overlap_counts(torch.from_numpy(prediction).to(device), torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device),
                                   classes).cpu().numpy()
         metric_list = []
@@ -129,8 +153,15 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), device
         return metric_list
     if zoom == "gpu":
         pred_d = predict_volume(image, net, patch_size, device=device, zoom="gpu")
+        if nms and cc == "host":
+            pred_d = torch.from_numpy(_cc_host.keep_largest_per_class(pred_d.cpu().numpy())).to(device)
     else:
-        pred_d = torch.from_numpy(_t2d.predict_volume(image, net, patch_size, device=device)).to(device)
+        prediction = _t2d.predict_volume(image, net, patch_size, device=device)
+        if nms and cc == "host":
+            prediction = _cc_host.keep_largest_per_class(prediction)
+        pred_d = torch.from_numpy(prediction).to(device)
+    if nms and cc == "gpu":
+        pred_d = _cc_gpu.largest_per_class(pred_d, classes)
     lab_d = torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device)
     cnt = _t2d.overlap_counts(pred_d, lab_d, classes).cpu().numpy()
     if classes <= 1:
@@ -224,18 +255,23 @@ def _metric_percase_3d_device(pred, gt, voxelspacing=None, connectivity=1):
 
 
 def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, preproc_fn=None,
-                  metric_detail=0, nms=0, device="cuda:0", surface="host", cc="host", voxelspacing=None, connectivity=1):
+                  metric_detail=0, nms=0, device="cuda:0", surface="host", cc="host", voxelspacing=None, connectivity=1,
+                  nms_mode="foreground"):
     """test_util.test_all_case: the mean (dice, jc, hd95, asd) over `cases` (an all-background prediction scores (0, 0, 0, 0)).
     cc="host" (default) takes the largest component of `nms` from test_util.getLargestCC on the host; cc="gpu" (with surface="gpu"
     only) is the device-resident tail: the label map of predict_case stays a device tensor, goes through cc_gpu.largest_cc with `nms`,
     and dice / jc / hd95 / asd come from the overlap-count and surface-distance kernels on it - no volume and no score map reach the
     host.  Like getLargestCC, cc_gpu.largest_cc takes every non-zero label as one foreground (skimage.measure.label, which the
-    reference calls, joins only voxels of the same value): equal for the two-class case `nms` is used on, not for more classes."""
+    reference calls, joins only voxels of the same value): equal for the two-class case `nms` is used on, not for more classes.
+    nms_mode (read only when `nms` is set) chooses what `nms` keeps: "foreground" (default) is that getLargestCC / largest_cc; "value" is
+    the reference's own meaning, the largest component of equal values (cc_host.getLargestCC_by_value / cc_gpu.largest_cc_by_value);
+    "per_class" keeps the largest component of every class (cc_host.keep_largest_per_class / cc_gpu.largest_per_class)."""
     _surface_gpu.check_route(surface)
     if _cc_gpu.check_cc(cc) == "gpu" and surface != "gpu":
         raise ValueError('cc="gpu" is the device-resident tail of surface="gpu"; got surface=%r' % (surface,))
+    mode = _check_nms_mode(nms_mode) if nms else "foreground"
     unit = _unit(voxelspacing, connectivity)
-    if surface == "host" and unit:
+    if surface == "host" and unit and mode == "foreground":
         return _t3d.test_all_case(model, cases, num_classes, patch_size=patch_size, stride_xy=stride_xy, stride_z=stride_z,
                                   preproc_fn=preproc_fn, metric_detail=metric_detail, nms=nms, device=device)
     if not unit:
@@ -247,13 +283,17 @@ def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_x
         if cc == "gpu":
             prediction = predict_case(model, image, stride_xy, stride_z, patch_size, num_classes, device=device)
             if nms:
-                prediction = _cc_gpu.largest_cc(prediction)
+                prediction = (_cc_gpu.largest_cc(prediction) if mode == "foreground" else
+                              _cc_gpu.largest_cc_by_value(prediction, num_classes) if mode == "value" else
+                              _cc_gpu.largest_per_class(prediction, num_classes))
             single = _metric_percase_3d_device(prediction, torch.from_numpy(np.asarray(label) != 0).to(prediction.device),
                                                voxelspacing, connectivity)
         else:
             prediction, _ = _t3d.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, device=device)
             if nms:
-                prediction = _t3d.getLargestCC(prediction)
+                prediction = (_t3d.getLargestCC(prediction) if mode == "foreground" else
+                              _cc_host.getLargestCC_by_value(prediction) if mode == "value" else
+                              _cc_host.keep_largest_per_class(prediction))
             single = ((0, 0, 0, 0) if np.sum(prediction) == 0 else
                       calculate_metric_percase_3d(prediction, np.asarray(label), surface, voxelspacing, connectivity))
         if metric_detail:

@@ -494,6 +494,25 @@ int arco_surface_sp_dist(const int64_t* pred, const int64_t* gt, int D, int H, i
 long arco_cc_ws_bytes(int D, int H, int W);
 int arco_cc_largest(const int64_t* x, int D, int H, int W, int ndim, int connectivity, void* ws, long ws_bytes, int32_t* labels,
                     long labels_bytes, uint8_t* largest, long largest_bytes, int64_t* info, long info_bytes, void* stream);
+/* ---- V  connected components BY VALUE and the largest one of every class (csrc/cc_value.hip, arco_amd/utils/cc_gpu.py): what
+ *      skimage.measure.label, which the reference's getLargestCC calls, means for more than two classes.  C = classes in 2..256.  A voxel
+ *      is in range when 1 <= x[v] <= C - 1; every other value (0, negatives, >= C) is background in all outputs.  Two in-range voxels are
+ *      connected when they are neighbours as above AND have equal values.
+ *        labels[v]  int32: 0 on background, else 1 + the smallest linear index of v's component;
+ *        keep[v]    uint8: 1 where v lies in the component of ITS OWN class with the most voxels (of several that large: the one whose
+ *                   first voxel comes first in memory);
+ *        info       int64[C + 1][3]: rows 1..C-1 = {components of class c, linear index of the winner's first voxel, its voxel count},
+ *                   {0, -1, 0} for an absent class; row 0 the same triple over all classes together (every component; the single one
+ *                   with the most voxels, ties to the first in memory); row C = {voxels with a value outside 0..C-1, linear index of
+ *                   the first of them or -1, 0}.
+ *      Integer arithmetic and order-independent: identical bits on every run.  ws: arco_cc_value_ws_bytes(D, H, W, classes) bytes, 8-byte
+ *      aligned (-1 for sizes or a class count the launch rejects).  ARCO_ERR_ARG before anything is launched or written for: a null
+ *      pointer, a dim < 1 or > 4096, D*H*W >= 2^31, classes outside 2..256, ndim not 2 or 3, ndim 2 with D != 1, connectivity outside
+ *      1..ndim, ws_bytes, labels_bytes (4 per voxel), keep_bytes (1 per voxel) or info_bytes (24 * (C + 1)) too small.              */
+long arco_cc_value_ws_bytes(int D, int H, int W, int classes);
+int arco_cc_value_largest(const int64_t* x, int D, int H, int W, int ndim, int connectivity, int classes, void* ws, long ws_bytes,
+                          int32_t* labels, long labels_bytes, uint8_t* keep, long keep_bytes, int64_t* info, long info_bytes,
+                          void* stream);
 /* ---- V  the zoom(order=0) round trip of 2-D evaluation (test_2D.py:72-88; csrc/zoom.hip, arco_amd/utils/zoom_gpu.py), bit for bit
  *      scipy.ndimage.zoom(order=0, mode='constant'): output index o of an axis of n_in points resampled to n_out >= 2 points reads input
  *      index floor(cc + 0.5), cc = (double)o * z, z = (n_in - 1) / (n_out - 1) computed by the caller in float64; the output is the
