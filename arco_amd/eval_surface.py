@@ -15,13 +15,13 @@ The metric functions, test_single_volume and test_all_case also take metrics.bin
 meaning: None is 1.0, a number is broadcast, a sequence has one entry per axis of the scored map - three for the [S, X, Y] volume of
 test_single_volume; connectivity 1..ndim).  With both at their defaults every function takes the path it took without them.  Otherwise
 surface="host" gives hd95 / asd from metrics.binary with the two arguments on the label map of the same predict functions, and
-surface="gpu" from surface_gpu.spaced_metrics / spaced_pair_metrics (float64 records, csrc/surface_sp.hip) on the device tensors that are
+surface="gpu" from surface_gpu.spaced_metrics / spaced_pair_metrics (float64 records, csrc/surface.hip) on the device tensors that are
 there already - zoom="gpu" and cc="gpu" included.  A bad spacing or connectivity is a ValueError before any GPU work.
 What `nms` keeps: test_all_case takes `nms_mode="foreground"` (default: getLargestCC / largest_cc, every non-zero label one foreground),
 "value" (the reference's own meaning through skimage.measure.label: the largest component of EQUAL values, cc_host.getLargestCC_by_value
 / cc_gpu.largest_cc_by_value) or "per_class" (the largest component of every class, cc_host.keep_largest_per_class /
 cc_gpu.largest_per_class); the keyword is read only when `nms` is set, any other value is a ValueError before any GPU work.
-test_single_volume takes `nms=0, cc="host"`: nms=1 keeps each class's largest component of the [S, X, Y] prediction (csrc/cc_value.hip on
+test_single_volume takes `nms=0, cc="host"`: nms=1 keeps each class's largest component of the [S, X, Y] prediction (csrc/cc.hip by value on
 cc="gpu", which needs surface="gpu") before the overlap counts and the surface metrics.
 Inference, the sliding window, the overlap counts and the empty-set conventions are those modules' own."""
 import numpy as np
@@ -43,7 +43,25 @@ def _unit(voxelspacing, connectivity):
     return voxelspacing is None and isinstance(connectivity, int) and connectivity == 1
 
 
-NMS_MODES = ("foreground", "value", "per_class")
+def _pair_device(pred, gt, voxelspacing, connectivity):
+    """(hd95, asd) of one mask pair from the surface kernels: the integer histogram at the defaults, else the float64 records."""
+    if _unit(voxelspacing, connectivity):
+        return _surface_gpu.pair_metrics(pred, gt)
+    return _surface_gpu.spaced_pair_metrics(pred, gt, voxelspacing, connectivity)
+
+
+def _classes_device(pred, gt, classes, voxelspacing, connectivity):
+    """[(hd95, asd) or None] per class of two label tensors on the device, by the same choice."""
+    if _unit(voxelspacing, connectivity):
+        return _surface_gpu.surface_metrics(pred, gt, classes)
+    return _surface_gpu.spaced_metrics(pred, gt, classes, voxelspacing, connectivity)
+
+
+# what `nms` keeps: nms_mode -> (host function of the label map, device function of the label map and the class count)
+_NMS = {"foreground": (_t3d.getLargestCC, lambda x, classes: _cc_gpu.largest_cc(x)),
+        "value": (_cc_host.getLargestCC_by_value, _cc_gpu.largest_cc_by_value),
+        "per_class": (_cc_host.keep_largest_per_class, _cc_gpu.largest_per_class)}
+NMS_MODES = tuple(_NMS)
 
 
 def _check_nms_mode(nms_mode):
@@ -55,6 +73,17 @@ def _check_nms_mode(nms_mode):
 
 def _shape(x):
     return tuple(x.shape) if torch.is_tensor(x) else np.shape(x)
+
+
+def _metric_list(cnt, classes, surface_of):
+    """test_single_volume's [(dice, jc, hd95, asd)] per class from the overlap counts; surface_of(c) is the (hd95, asd) of a class that
+    both volumes hold, the others get (0.0, 0.0)."""
+    metric_list = []
+    for c in range(1, classes):
+        dice, jc = _t2d._dice_jc(int(cnt[c, 0]), int(cnt[c, 1]), int(cnt[c, 2]))
+        hd95, asd = surface_of(c) if cnt[c, 0] > 0 and cnt[c, 1] > 0 else (0.0, 0.0)
+        metric_list.append((dice, jc, hd95, asd))
+    return metric_list
 
 
 def calculate_metric_percase_2d(pred, gt, surface="host", voxelspacing=None, connectivity=1):
@@ -79,10 +108,7 @@ def calculate_metric_percase_2d(pred, gt, surface="host", voxelspacing=None, con
     dice, jc = _t2d._dice_jc(n_pred, n_gt, n_both)
     hd95 = asd = 0.0
     if n_pred > 0 and n_gt > 0:
-        if unit:
-            hd95, asd = _surface_gpu.pair_metrics(p, g)
-        else:
-            hd95, asd = _surface_gpu.spaced_pair_metrics(p, g, voxelspacing, connectivity)
+        hd95, asd = _pair_device(p, g, voxelspacing, connectivity)
     return dice, jc, hd95, asd
 
 
@@ -142,15 +168,8 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), device
             prediction = _cc_host.keep_largest_per_class(prediction)
         cnt = _t2d.overlap_counts(torch.from_numpy(prediction).to(device), torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device),
                                   classes).cpu().numpy()
-        metric_list = []
-        for c in range(1, classes):
-            dice, jc = _t2d._dice_jc(int(cnt[c, 0]), int(cnt[c, 1]), int(cnt[c, 2]))
-            hd95 = asd = 0.0
-            if cnt[c, 0] > 0 and cnt[c, 1] > 0:
-                asd = _binary.asd(prediction == c, label == c, voxelspacing, connectivity)
-                hd95 = _binary.hd95(prediction == c, label == c, voxelspacing, connectivity)
-            metric_list.append((dice, jc, hd95, asd))
-        return metric_list
+        return _metric_list(cnt, classes, lambda c: (_binary.hd95(prediction == c, label == c, voxelspacing, connectivity),
+                                                     _binary.asd(prediction == c, label == c, voxelspacing, connectivity)))
     if zoom == "gpu":
         pred_d = predict_volume(image, net, patch_size, device=device, zoom="gpu")
         if nms and cc == "host":
@@ -164,20 +183,8 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), device
         pred_d = _cc_gpu.largest_per_class(pred_d, classes)
     lab_d = torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device)
     cnt = _t2d.overlap_counts(pred_d, lab_d, classes).cpu().numpy()
-    if classes <= 1:
-        scored = []
-    elif unit:
-        scored = _surface_gpu.surface_metrics(pred_d, lab_d, range(1, classes))
-    else:
-        scored = _surface_gpu.spaced_metrics(pred_d, lab_d, range(1, classes), voxelspacing, connectivity)
-    metric_list = []
-    for c in range(1, classes):
-        dice, jc = _t2d._dice_jc(int(cnt[c, 0]), int(cnt[c, 1]), int(cnt[c, 2]))
-        hd95 = asd = 0.0
-        if cnt[c, 0] > 0 and cnt[c, 1] > 0:
-            hd95, asd = scored[c - 1]
-        metric_list.append((dice, jc, hd95, asd))
-    return metric_list
+    scored = [] if classes <= 1 else _classes_device(pred_d, lab_d, range(1, classes), voxelspacing, connectivity)
+    return _metric_list(cnt, classes, lambda c: scored[c - 1])
 
 
 def calculate_metric_percase_3d(pred, gt, surface="host", voxelspacing=None, connectivity=1):
@@ -185,13 +192,12 @@ def calculate_metric_percase_3d(pred, gt, surface="host", voxelspacing=None, con
     unit = _unit(voxelspacing, connectivity)
     if _surface_gpu.check_route(surface) == "host" and unit:
         return _t3d.calculate_metric_percase(pred, gt)
-    if unit:
-        return (_binary.dc(pred, gt), _binary.jc(pred, gt)) + _surface_gpu.pair_metrics(pred, gt)
-    _surface_gpu.check_spaced_args(voxelspacing, connectivity, len(_shape(pred)))
+    if not unit:
+        _surface_gpu.check_spaced_args(voxelspacing, connectivity, len(_shape(pred)))
     if surface == "host":
         return (_binary.dc(pred, gt), _binary.jc(pred, gt), _binary.hd95(pred, gt, voxelspacing, connectivity),
                 _binary.asd(pred, gt, voxelspacing, connectivity))
-    return (_binary.dc(pred, gt), _binary.jc(pred, gt)) + _surface_gpu.spaced_pair_metrics(pred, gt, voxelspacing, connectivity)
+    return (_binary.dc(pred, gt), _binary.jc(pred, gt)) + _pair_device(pred, gt, voxelspacing, connectivity)
 
 
 @torch.no_grad()
@@ -249,9 +255,7 @@ def _metric_percase_3d_device(pred, gt, voxelspacing=None, connectivity=1):
         return (0, 0, 0, 0)
     dice = 2.0 * n_both / float(n_pred + n_gt)                                   # metrics.binary.dc / jc on the counts
     jc = float(n_both) / float(n_pred + n_gt - n_both)
-    if _unit(voxelspacing, connectivity):
-        return (dice, jc) + _surface_gpu.pair_metrics(p, g)
-    return (dice, jc) + _surface_gpu.spaced_pair_metrics(p, g, voxelspacing, connectivity)
+    return (dice, jc) + _pair_device(p, g, voxelspacing, connectivity)
 
 
 def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, preproc_fn=None,
@@ -283,17 +287,13 @@ def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_x
         if cc == "gpu":
             prediction = predict_case(model, image, stride_xy, stride_z, patch_size, num_classes, device=device)
             if nms:
-                prediction = (_cc_gpu.largest_cc(prediction) if mode == "foreground" else
-                              _cc_gpu.largest_cc_by_value(prediction, num_classes) if mode == "value" else
-                              _cc_gpu.largest_per_class(prediction, num_classes))
+                prediction = _NMS[mode][1](prediction, num_classes)
             single = _metric_percase_3d_device(prediction, torch.from_numpy(np.asarray(label) != 0).to(prediction.device),
                                                voxelspacing, connectivity)
         else:
             prediction, _ = _t3d.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, device=device)
             if nms:
-                prediction = (_t3d.getLargestCC(prediction) if mode == "foreground" else
-                              _cc_host.getLargestCC_by_value(prediction) if mode == "value" else
-                              _cc_host.keep_largest_per_class(prediction))
+                prediction = _NMS[mode][0](prediction)
             single = ((0, 0, 0, 0) if np.sum(prediction) == 0 else
                       calculate_metric_percase_3d(prediction, np.asarray(label), surface, voxelspacing, connectivity))
         if metric_detail:

@@ -14,7 +14,7 @@ Like getLargestCC - and unlike skimage.measure.label, which the reference calls 
 non-zero label is one foreground.  The two agree on the binary maps the reference uses `nms` on and would differ for more than two
 classes; the host function stays as it is and this route is pinned to it.
 
-The BY-VALUE meaning (csrc/cc_value.hip) stands beside it, for label maps of `classes` classes (2..256): a voxel is in range when
+The BY-VALUE meaning (the ccv_* kernels of csrc/cc.hip) stands beside it, for label maps of `classes` classes (2..256): a voxel is in range when
 1 <= x <= classes - 1, and two in-range voxels are connected only when they are neighbours AND have equal values.
   components_by_value(x, classes, connectivity, ndim) -> (labels, keep, info), all on the device
     labels   int32: 0 on background (anything not in range), else 1 + the smallest linear index of the voxel's component
@@ -31,6 +31,7 @@ from .. import _lib as L
 
 MAX_DIM = 4096          # csrc/cc.hip CC_MAXDIM
 MAX_VOXELS = 1 << 31    # exclusive: linear indices are int32
+MAX_CLASSES = 256       # csrc/cc.hip CCV_MAXCLASSES: classes are kept as bytes
 ROUTES = ("host", "gpu")
 
 
@@ -41,14 +42,23 @@ def check_cc(cc):
     return cc
 
 
-def components(x, connectivity=None, ndim=None):
-    """(labels int32, largest uint8, info int64 [3]) on the device for one integer label tensor (2-D or 3-D, on the GPU).
-    ndim (default: the tensor's rank) says how many axes there are: a [1, H, W] tensor with ndim=2 is the map [H, W], an [H, W] tensor
-    with ndim=3 the one-slice volume [1, H, W].  connectivity in 1..ndim (default ndim: 8 neighbours in 2-D, 26 in 3-D)."""
+def _check_classes(classes):
+    if isinstance(classes, bool) or not isinstance(classes, (int, np.integer)):
+        raise TypeError(f"classes must be an int, got {classes!r}")
+    if not 2 <= classes <= MAX_CLASSES:
+        raise ValueError(f"classes must be in 2..{MAX_CLASSES}, got {classes}")
+    return int(classes)
+
+
+def _check_map(name, x, connectivity, ndim, *classes):
+    """The argument checks of `components` and `components_by_value` (`name`; the latter passes its `classes`, checked in their
+    place), all before any GPU work; (D, H, W, ndim, connectivity) with the defaults filled in."""
     if not torch.is_tensor(x):
-        raise TypeError("components takes a torch tensor on the GPU")
+        raise TypeError(f"{name} takes a torch tensor on the GPU")
     if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
-        raise TypeError("components takes an integer label tensor")
+        raise TypeError(f"{name} takes an integer label tensor")
+    for c in classes:
+        _check_classes(c)
     if x.dim() not in (2, 3):
         raise ValueError(f"the label map must be 2-D or 3-D, got shape {tuple(x.shape)}")
     ndim = x.dim() if ndim is None else int(ndim)
@@ -63,6 +73,21 @@ def components(x, connectivity=None, ndim=None):
         raise ValueError(f"at most 2^31 - 1 voxels, got shape {tuple(x.shape)}")
     L.require_gpu(x)
     D, H, W = (1, *x.shape) if x.dim() == 2 else x.shape
+    return D, H, W, ndim, connectivity
+
+
+def _to_device(t, device):
+    """The tensor on `device`; by default where it is when that is a GPU, else on cuda:0."""
+    if device is None:
+        device = t.device if t.is_cuda else "cuda:0"
+    return t.to(device)
+
+
+def components(x, connectivity=None, ndim=None):
+    """(labels int32, largest uint8, info int64 [3]) on the device for one integer label tensor (2-D or 3-D, on the GPU).
+    ndim (default: the tensor's rank) says how many axes there are: a [1, H, W] tensor with ndim=2 is the map [H, W], an [H, W] tensor
+    with ndim=3 the one-slice volume [1, H, W].  connectivity in 1..ndim (default ndim: 8 neighbours in 2-D, 26 in 3-D)."""
+    D, H, W, ndim, connectivity = _check_map("components", x, connectivity, ndim)
     v = x.to(torch.int64).contiguous()
     ws_bytes = L.query("arco_cc_ws_bytes", D, H, W)
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=v.device)
@@ -79,9 +104,7 @@ def largest_cc(x, device=None):
     """test_util.getLargestCC on the GPU: the largest component (full connectivity) of `x != 0` (numpy or torch, 2-D or 3-D) as a bool
     tensor on the device.  AssertionError when there is no foreground, as the host function."""
     t = x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x) != 0)          # (a fresh bool array: one byte per voxel to upload)
-    if device is None:
-        device = t.device if t.is_cuda else "cuda:0"
-    t = t.to(device)
+    t = _to_device(t, device)
     if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
         t = (t != 0).to(torch.uint8)
     _, largest, info = components(t)
@@ -89,40 +112,12 @@ def largest_cc(x, device=None):
     return largest.bool()
 
 
-MAX_CLASSES = 256       # csrc/cc_value.hip CCV_MAXCLASSES: classes are kept as bytes
-
-
-def _check_classes(classes):
-    if isinstance(classes, bool) or not isinstance(classes, (int, np.integer)):
-        raise TypeError(f"classes must be an int, got {classes!r}")
-    if not 2 <= classes <= MAX_CLASSES:
-        raise ValueError(f"classes must be in 2..{MAX_CLASSES}, got {classes}")
-    return int(classes)
-
-
 def components_by_value(x, classes, connectivity=None, ndim=None):
     """(labels int32, keep uint8, info int64 [classes + 1, 3]) on the device for one integer label tensor (2-D or 3-D, on the GPU): the
     components of equal values and the largest one of every class (module docstring).  The tensor, ndim, connectivity and size rules are
     those of `components`; classes in 2..256.  Nothing is synchronised."""
-    if not torch.is_tensor(x):
-        raise TypeError("components_by_value takes a torch tensor on the GPU")
-    if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
-        raise TypeError("components_by_value takes an integer label tensor")
-    classes = _check_classes(classes)
-    if x.dim() not in (2, 3):
-        raise ValueError(f"the label map must be 2-D or 3-D, got shape {tuple(x.shape)}")
-    ndim = x.dim() if ndim is None else int(ndim)
-    if ndim not in (2, 3) or (ndim == 2 and x.dim() == 3 and x.shape[0] != 1):
-        raise ValueError(f"ndim must be 2 or 3, and 2 only for a map [H, W] or [1, H, W]; got shape {tuple(x.shape)} and ndim {ndim}")
-    connectivity = ndim if connectivity is None else int(connectivity)
-    if not 1 <= connectivity <= ndim:
-        raise ValueError(f"connectivity must be in 1..{ndim}, got {connectivity}")
-    if min(x.shape) < 1 or max(x.shape) > MAX_DIM:
-        raise ValueError(f"every dim must be in 1..{MAX_DIM}, got {tuple(x.shape)}")
-    if x.numel() >= MAX_VOXELS:
-        raise ValueError(f"at most 2^31 - 1 voxels, got shape {tuple(x.shape)}")
-    L.require_gpu(x)
-    D, H, W = (1, *x.shape) if x.dim() == 2 else x.shape
+    D, H, W, ndim, connectivity = _check_map("components_by_value", x, connectivity, ndim, classes)
+    classes = int(classes)
     v = x.to(torch.int64).contiguous()
     ws_bytes = L.query("arco_cc_value_ws_bytes", D, H, W, classes)
     ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=v.device)
@@ -145,11 +140,9 @@ def _label_tensor(x, device):
         raise TypeError("a label map by value must be of an integer (or bool) type")
     if t.dim() not in (2, 3):
         raise ValueError(f"the label map must be 2-D or 3-D, got shape {tuple(t.shape)}")
-    if device is None:
-        device = t.device if t.is_cuda else "cuda:0"
     if t.dtype == torch.bool:
         t = t.to(torch.uint8)
-    return t.to(device)
+    return _to_device(t, device)
 
 
 def _refuse_out_of_range(t, classes, info):

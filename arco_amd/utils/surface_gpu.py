@@ -9,7 +9,7 @@ finishes in float64 with numpy's own percentile:
   v = repeat(sqrt(k), count);  hd95 = percentile(v of both directions pooled, 95);  asd = mean(v of direction 0)
 sqrt of the integer k is bit for bit what distance_transform_edt returns at that voxel, so hd95 equals the host route exactly and asd
 up to the order of one float64 sum.  Anisotropic spacing breaks the integer histogram: a `voxelspacing` or a `connectivity` other
-than 1 takes the float64 record kernels (csrc/surface_sp.hip) through the `spaced_*` functions at the end of this module, which return
+than 1 takes the float64 record route of the same file through the `spaced_*` functions at the end of this module, which return
 one squared distance per border voxel; `pair_metrics` / `hd95` / `asd` stay the integer-exact unit-spacing route and refuse both."""
 import numpy as np
 import torch
@@ -45,28 +45,42 @@ def _class_range(classes):
     return cls[0], cls[-1]
 
 
+def _map_ndim(shape, ndim):
+    if len(shape) not in (2, 3):
+        raise ValueError(f"label maps must be 2-D or 3-D, got shape {tuple(shape)}")
+    ndim = len(shape) if ndim is None else int(ndim)
+    if ndim not in (2, 3) or (ndim == 2 and len(shape) == 3 and shape[0] != 1):
+        raise ValueError(f"ndim must be 2 or 3, and 2 only for a map [H, W] or [1, H, W]; got shape {tuple(shape)} and ndim {ndim}")
+    if min(shape) < 1 or max(shape) > MAX_DIM:
+        raise ValueError(f"every dim must be in 1..{MAX_DIM}, got {tuple(shape)}")
+    return ndim
+
+
+def _check_pair(who, pred, gt, ndim):
+    """The checks of the two label tensors of a launch (`who` takes them, for the messages); the map's ndim."""
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)):
+        raise TypeError(f"{who} torch tensors on the GPU")
+    if pred.dtype.is_floating_point or gt.dtype.is_floating_point or pred.dtype == torch.bool or gt.dtype == torch.bool:
+        raise TypeError(f"{who} integer label tensors")
+    if pred.shape != gt.shape:
+        raise ValueError(f"shapes differ: {tuple(pred.shape)} vs {tuple(gt.shape)}")
+    return _map_ndim(tuple(pred.shape), ndim)
+
+
+def _launch_pair(pred, gt):
+    """(D, H, W, pred, gt) as a launch takes them: on the GPU, int64, contiguous."""
+    L.require_gpu(pred, gt)
+    D, H, W = (1, *pred.shape) if pred.dim() == 2 else pred.shape
+    return D, H, W, pred.to(torch.int64).contiguous(), gt.to(torch.int64).contiguous()
+
+
 def surface_histograms(pred, gt, classes, ndim=None):
     """int64 [len(classes), 2, nbins(shape)] on the device for two integer label tensors (2-D or 3-D, same shape, on the GPU).
     ndim (default: the tensors' rank) says how many axes have neighbours: a [1, H, W] tensor with ndim=2 is the 2-D map [H, W], and
     an [H, W] tensor with ndim=3 is the one-slice volume [1, H, W], whose every voxel is a border voxel (its z neighbours lie outside)."""
     c_lo, c_hi = _class_range(classes)
-    if not (torch.is_tensor(pred) and torch.is_tensor(gt)):
-        raise TypeError("surface_histograms takes torch tensors on the GPU")
-    if pred.dtype.is_floating_point or gt.dtype.is_floating_point or pred.dtype == torch.bool or gt.dtype == torch.bool:
-        raise TypeError("surface_histograms takes integer label tensors")
-    if pred.shape != gt.shape:
-        raise ValueError(f"shapes differ: {tuple(pred.shape)} vs {tuple(gt.shape)}")
-    if pred.dim() not in (2, 3):
-        raise ValueError(f"label maps must be 2-D or 3-D, got shape {tuple(pred.shape)}")
-    ndim = pred.dim() if ndim is None else int(ndim)
-    if ndim not in (2, 3) or (ndim == 2 and pred.dim() == 3 and pred.shape[0] != 1):
-        raise ValueError(f"ndim must be 2 or 3, and 2 only for a map [H, W] or [1, H, W]; got shape {tuple(pred.shape)} and ndim {ndim}")
-    if min(pred.shape) < 1 or max(pred.shape) > MAX_DIM:
-        raise ValueError(f"every dim must be in 1..{MAX_DIM}, got {tuple(pred.shape)}")
-    L.require_gpu(pred, gt)
-    D, H, W = (1, *pred.shape) if pred.dim() == 2 else pred.shape
-    p = pred.to(torch.int64).contiguous()
-    g = gt.to(torch.int64).contiguous()
+    ndim = _check_pair("surface_histograms takes", pred, gt, ndim)
+    D, H, W, p, g = _launch_pair(pred, gt)
     nc, nb = c_hi - c_lo + 1, nbins(pred.shape)
     ws_bytes = L.query("arco_surface_ws_bytes", D, H, W, nc)
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=p.device)
@@ -80,12 +94,16 @@ def _distances(bins, counts):
     return np.repeat(np.sqrt(np.asarray(bins).astype(np.float64)), np.asarray(counts))
 
 
-def finish(bins0, counts0, bins1, counts1):
-    """(hd95, asd) in float64 from the non-empty bins of the two directions; None when a direction is empty."""
-    v0, v1 = _distances(bins0, counts0), _distances(bins1, counts1)
-    if v0.size == 0 or v1.size == 0:
+def finish_distances(d0, d1):
+    """(hd95, asd) in float64 from the distances of the two directions; None when a direction is empty."""
+    if d0.size == 0 or d1.size == 0:
         return None
-    return float(np.percentile(np.hstack((v0, v1)), 95)), float(v0.mean())
+    return float(np.percentile(np.hstack((d0, d1)), 95)), float(d0.mean())
+
+
+def finish(bins0, counts0, bins1, counts1):
+    """`finish_distances` from the non-empty bins of the two directions."""
+    return finish_distances(_distances(bins0, counts0), _distances(bins1, counts1))
 
 
 def finish_histogram(hist):
@@ -125,17 +143,22 @@ def _mask(x, device):
     return (t.to(device) > 0).to(torch.int64)
 
 
-def pair_metrics(result, reference, voxelspacing=None, connectivity=1, device=None):
-    """(hd95, asd) of one pair of binary masks (`> 0`; numpy or torch, 2-D or 3-D) from ONE histogram call.  Raises
-    metrics.binary's RuntimeError when a mask is empty."""
-    _binary_args(voxelspacing, connectivity)
+def _pair(metrics, result, reference, device, *args):
+    """(hd95, asd) of one pair of binary masks from metrics(pred, gt, (1,), *args); metrics.binary's RuntimeError for an empty mask."""
     a = _mask(result, device)
     b = _mask(reference, a.device)
-    got = surface_metrics(a, b, (1,))[0]
+    got = metrics(a, b, (1,), *args)[0]
     if got is None:
         any_a, any_b = torch.stack((a.any(), b.any())).cpu().tolist()
         raise RuntimeError(_EMPTY[0] if not any_a else _EMPTY[1])
     return got
+
+
+def pair_metrics(result, reference, voxelspacing=None, connectivity=1, device=None):
+    """(hd95, asd) of one pair of binary masks (`> 0`; numpy or torch, 2-D or 3-D) from ONE histogram call.  Raises
+    metrics.binary's RuntimeError when a mask is empty."""
+    _binary_args(voxelspacing, connectivity)
+    return _pair(surface_metrics, result, reference, device)
 
 
 def hd95(result, reference, voxelspacing=None, connectivity=1, device=None):
@@ -148,7 +171,7 @@ def asd(result, reference, voxelspacing=None, connectivity=1, device=None):
     return pair_metrics(result, reference, voxelspacing, connectivity, device)[1]
 
 
-# ---- a voxel spacing and a connectivity: float64 records instead of the integer histogram (csrc/surface_sp.hip) ---------------------------
+# ---- a voxel spacing and a connectivity: float64 records instead of the integer histogram (arco_surface_sp_dist) --------------------------
 def _spacing(voxelspacing, ndim):
     """medpy's voxelspacing for a map of `ndim` axes as a tuple of floats: None is 1.0, a scalar is broadcast, a sequence has one entry
     per axis."""
@@ -170,17 +193,6 @@ def _connectivity(connectivity, ndim):
     return int(connectivity)
 
 
-def _map_ndim(shape, ndim):
-    if len(shape) not in (2, 3):
-        raise ValueError(f"label maps must be 2-D or 3-D, got shape {tuple(shape)}")
-    ndim = len(shape) if ndim is None else int(ndim)
-    if ndim not in (2, 3) or (ndim == 2 and len(shape) == 3 and shape[0] != 1):
-        raise ValueError(f"ndim must be 2 or 3, and 2 only for a map [H, W] or [1, H, W]; got shape {tuple(shape)} and ndim {ndim}")
-    if min(shape) < 1 or max(shape) > MAX_DIM:
-        raise ValueError(f"every dim must be in 1..{MAX_DIM}, got {tuple(shape)}")
-    return ndim
-
-
 def check_spaced_args(voxelspacing, connectivity, ndim):
     """ValueError for a voxelspacing or a connectivity that a map of `ndim` axes cannot take; (spacing per axis, connectivity)."""
     return _spacing(voxelspacing, ndim), _connectivity(connectivity, ndim)
@@ -190,23 +202,14 @@ def spaced_launch(pred, gt, classes, voxelspacing=None, connectivity=1, ndim=Non
     """One arco_surface_sp_dist call for two integer label tensors on the GPU: (val float64 [cap], tag int32 [cap], count int64 [1]) ON
     THE DEVICE, not waited for.  Every argument check comes before any GPU work.  cap defaults to 2 * voxels, which cannot overflow."""
     c_lo, c_hi = _class_range(classes)
-    if not (torch.is_tensor(pred) and torch.is_tensor(gt)):
-        raise TypeError("the spaced surface functions take torch tensors on the GPU")
-    if pred.dtype.is_floating_point or gt.dtype.is_floating_point or pred.dtype == torch.bool or gt.dtype == torch.bool:
-        raise TypeError("the spaced surface functions take integer label tensors")
-    if pred.shape != gt.shape:
-        raise ValueError(f"shapes differ: {tuple(pred.shape)} vs {tuple(gt.shape)}")
-    ndim = _map_ndim(tuple(pred.shape), ndim)
+    ndim = _check_pair("the spaced surface functions take", pred, gt, ndim)
     sp = _spacing(voxelspacing, ndim)
     conn = _connectivity(connectivity, ndim)
     cap = 2 * pred.numel() if cap is None else int(cap)
     if cap < 1:
         raise ValueError(f"cap must be at least 1, got {cap}")
-    L.require_gpu(pred, gt)
-    D, H, W = (1, *pred.shape) if pred.dim() == 2 else pred.shape
+    D, H, W, p, g = _launch_pair(pred, gt)
     sz, sy, sx = (1.0, *sp) if ndim == 2 else sp
-    p = pred.to(torch.int64).contiguous()
-    g = gt.to(torch.int64).contiguous()
     ws_bytes = L.query("arco_surface_sp_ws_bytes", D, H, W, c_hi - c_lo + 1)
     ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=p.device)
     val = torch.empty(cap, dtype=torch.float64, device=p.device)
@@ -238,13 +241,6 @@ def spaced_distances(pred, gt, classes, voxelspacing=None, connectivity=1, ndim=
     return [tuple(np.sqrt(np.sort(val[tag == 2 * c + d])) for d in (0, 1)) for c in range(len(classes))]
 
 
-def finish_distances(d0, d1):
-    """(hd95, asd) in float64 from the distances of the two directions; None when a direction is empty."""
-    if d0.size == 0 or d1.size == 0:
-        return None
-    return float(np.percentile(np.hstack((d0, d1)), 95)), float(d0.mean())
-
-
 def spaced_metrics(pred, gt, classes, voxelspacing=None, connectivity=1):
     """[(hd95, asd) or None] per class, as surface_metrics, with metrics.binary's voxelspacing and connectivity."""
     return [finish_distances(d0, d1) for d0, d1 in spaced_distances(pred, gt, classes, voxelspacing, connectivity)]
@@ -255,13 +251,7 @@ def spaced_pair_metrics(result, reference, voxelspacing=None, connectivity=1, de
     binary masks from ONE call.  ValueError for a bad argument before any GPU work; metrics.binary's RuntimeError for an empty mask."""
     ndim = _map_ndim(tuple(result.shape if torch.is_tensor(result) else np.shape(result)), None)
     check_spaced_args(voxelspacing, connectivity, ndim)
-    a = _mask(result, device)
-    b = _mask(reference, a.device)
-    got = spaced_metrics(a, b, (1,), voxelspacing, connectivity)[0]
-    if got is None:
-        any_a, any_b = torch.stack((a.any(), b.any())).cpu().tolist()
-        raise RuntimeError(_EMPTY[0] if not any_a else _EMPTY[1])
-    return got
+    return _pair(spaced_metrics, result, reference, device, voxelspacing, connectivity)
 
 
 def spaced_hd95(result, reference, voxelspacing=None, connectivity=1, device=None):

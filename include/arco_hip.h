@@ -494,7 +494,7 @@ int arco_surface_sp_dist(const int64_t* pred, const int64_t* gt, int D, int H, i
 long arco_cc_ws_bytes(int D, int H, int W);
 int arco_cc_largest(const int64_t* x, int D, int H, int W, int ndim, int connectivity, void* ws, long ws_bytes, int32_t* labels,
                     long labels_bytes, uint8_t* largest, long largest_bytes, int64_t* info, long info_bytes, void* stream);
-/* ---- V  connected components BY VALUE and the largest one of every class (csrc/cc_value.hip, arco_amd/utils/cc_gpu.py): what
+/* ---- V  connected components BY VALUE and the largest one of every class (csrc/cc.hip, arco_amd/utils/cc_gpu.py): what
  *      skimage.measure.label, which the reference's getLargestCC calls, means for more than two classes.  C = classes in 2..256.  A voxel
  *      is in range when 1 <= x[v] <= C - 1; every other value (0, negatives, >= C) is background in all outputs.  Two in-range voxels are
  *      connected when they are neighbours as above AND have equal values.

@@ -1,4 +1,4 @@
-"""Cases, references and checkers for the connected-components-by-value kernels (arco_amd/csrc/cc_value.hip, arco_amd/utils/cc_gpu.py).
+"""Cases, references and checkers for the connected-components-by-value kernels (arco_amd/csrc/cc.hip, arco_amd/utils/cc_gpu.py).
 
 The kernels return, for an integer label volume, a class count C (2..256) and a connectivity c in 1..ndim (scipy's
 generate_binary_structure(ndim, c)) - a voxel is IN RANGE when 1 <= x <= C - 1, two in-range voxels are connected when they are

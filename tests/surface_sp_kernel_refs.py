@@ -1,5 +1,5 @@
 """Cases, references and checkers for the surface-distance kernels with a voxel spacing and a connectivity
-(arco_amd/csrc/surface_sp.hip, the spaced_* functions of arco_amd/utils/surface_gpu.py).
+(arco_amd/csrc/surface.hip, the spaced_* functions of arco_amd/utils/surface_gpu.py).
 
 The kernels return one record per border voxel of A with a border voxel of B to measure to: val = the float64 SQUARED distance,
 tag = class index * 2 + direction (direction 0: A = pred == c, B = gt == c; 1 the other way round).  With
@@ -32,7 +32,7 @@ from arco_amd.utils import metrics
 GUARD, SENT32, SENT64 = R.GUARD, R.SENT32, R.SENT64
 BRUTE_MAX_VOXELS = R.BRUTE_MAX_VOXELS       # the brute force builds an |border A| x |border B| table; both are within the volume
 REL_SCIPY = 4 * 2.0 ** -52
-TILE = 128                                   # csrc/surface_sp.hip SP_TL
+TILE = 128                                   # csrc/surface.hip: the float64 tile of sf_minplus_kernel
 
 SPACINGS = {
     "10_1.25_1.25": (10.0, 1.25, 1.25),      # ACDC

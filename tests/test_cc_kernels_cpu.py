@@ -115,6 +115,13 @@ def test_exports_and_workspace_query():
         assert L.query("arco_cc_ws_bytes", *shape) == -1, shape
 
 
+def test_workspace_sizes_are_exact():
+    """The layout of CcWs: a 16-byte header, 8 bytes per row word, parent (4 bytes per voxel, padded to 8) and count (4 per voxel)."""
+    import arco_amd._lib as L
+    assert L.query("arco_cc_ws_bytes", 3, 4, 65) == 16 + 12 * 2 * 8 + 780 * 4 + 780 * 4 == 6448
+    assert L.query("arco_cc_ws_bytes", 1, 1, 9) == 16 + 1 * 8 + 10 * 4 + 9 * 4 == 100
+
+
 def test_argument_checks_reject_on_the_host():
     """ARCO_ERR_ARG (-1) is returned before anything is launched, so this needs no GPU; the pointers are host addresses (or null) that
     are never dereferenced."""

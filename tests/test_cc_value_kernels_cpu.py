@@ -1,4 +1,4 @@
-"""Connected components by value (arco_amd/csrc/cc_value.hip, arco_amd/utils/cc_gpu.py, arco_amd/utils/cc_host.py), the part that needs no
+"""Connected components by value (arco_amd/csrc/cc.hip, arco_amd/utils/cc_gpu.py, arco_amd/utils/cc_host.py), the part that needs no
 GPU:
   references    scipy_ref and the scipy-free flood fill of tests/cc_value_kernel_refs.py agree on every small case at every connectivity;
                 on a binary map scipy_ref is cc_kernel_refs.scipy_ref and getLargestCC_by_value is getLargestCC
@@ -195,6 +195,14 @@ def test_exports_and_workspace_query():
         assert L.query("arco_cc_value_ws_bytes", *shape, 3) == -1, shape
     for classes in (-1, 0, 1, 257, 1 << 16):
         assert L.query("arco_cc_value_ws_bytes", 2, 3, 4, classes) == -1, classes
+
+
+def test_workspace_sizes_are_exact():
+    """The layout of CcvWs: a header of 12 bytes per class plus 8 (padded to 8), two sets of row words of 8 bytes, parent and count
+    (4 bytes per voxel each, padded to 8) and the class bytes (padded to 8)."""
+    import arco_amd._lib as L
+    assert L.query("arco_cc_value_ws_bytes", 3, 4, 65, 3) == 48 + 2 * 12 * 2 * 8 + 2 * 780 * 4 + 784 == 7456
+    assert L.query("arco_cc_value_ws_bytes", 1, 1, 9, 2) == 32 + 2 * 1 * 8 + 2 * 10 * 4 + 16 == 144
 
 
 def test_argument_checks_reject_on_the_host():

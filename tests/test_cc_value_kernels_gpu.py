@@ -1,4 +1,4 @@
-"""Connected components by value (arco_amd/csrc/cc_value.hip) on the GPU against the scipy reference of tests/cc_value_kernel_refs.py
+"""Connected components by value (arco_amd/csrc/cc.hip) on the GPU against the scipy reference of tests/cc_value_kernel_refs.py
 (which tests/test_cc_value_kernels_cpu.py holds to a scipy-free flood fill and to the host functions of arco_amd/utils/cc_host.py).  Labels, the kept
 components and the counts are integers with one canonical value each, so every check is equality."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Surface-distance kernels with a voxel spacing and a connectivity (arco_amd/csrc/surface_sp.hip), the part that needs no GPU:
+"""Surface-distance kernels with a voxel spacing and a connectivity (arco_amd/csrc/surface.hip), the part that needs no GPU:
   border        the O(n^2) border of tests/surface_sp_kernel_refs.py equals X ^ binary_erosion(X, generate_binary_structure(ndim, c))
   references    sqrt of the brute force is within REL_SCIPY (4 * 2^-52, derived in the refs module) of scipy on every case, spacing and
                 connectivity, and array_equal to it with spacing (1, 1, 1)

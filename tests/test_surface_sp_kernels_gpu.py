@@ -1,4 +1,4 @@
-"""Surface-distance kernels with a voxel spacing and a connectivity (arco_amd/csrc/surface_sp.hip) on the GPU against the brute force of
+"""Surface-distance kernels with a voxel spacing and a connectivity (arco_amd/csrc/surface.hip) on the GPU against the brute force of
 tests/surface_sp_kernel_refs.py, which restates the kernels' operation order: the records, grouped by tag and sorted, are array_equal
 as float64 squared distances (tests/test_surface_sp_kernels_cpu.py holds that brute force to scipy).  hd95 / asd finished from them are
 held to metrics.binary with the same arguments at rtol 1e-12: per distance the two differ by at most REL_SCIPY = 4 * 2^-52 (derived

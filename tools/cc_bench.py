@@ -15,7 +15,7 @@ two evaluation routes with each other (dice, jc, hd95 ==, asd to 1e-12).
 Every step runs in a child process of its own under --step-timeout seconds; the first step that fails or runs out of time ends the
 run (nothing more is started on the GPU after it).
 
---by_value measures the by-value kernels (csrc/cc_value.hip) instead: label maps of 3 / 3 / 4 / 9 classes (--classes: that many for every
+--by_value measures the by-value kernels (csrc/cc.hip) instead: label maps of 3 / 3 / 4 / 9 classes (--classes: that many for every
 volume) at 112x112x80, 192x160x88 and twice 10x256x256 - one ball per class with 0.2 % speckle of random classes, and 30 % random
 density.  Per input the host route cc_host.keep_largest_per_class, cc_gpu.components_by_value and the binary cc_gpu.components on the
 same map's `!= 0` between device events, largest_per_class on a device tensor and from the numpy array, and largest_cc from the
@@ -138,7 +138,7 @@ def step_eval(shape_name, args):
     return res
 
 
-# ---- --by_value: components of equal values, the largest one of every class (csrc/cc_value.hip) ----------------------------------------
+# ---- --by_value: components of equal values, the largest one of every class (csrc/cc.hip) ----------------------------------------
 BV_VOLUMES = (("112x112x80", (112, 112, 80), 3), ("192x160x88", (192, 160, 88), 3), ("10x256x256", (10, 256, 256), 4),
               ("10x256x256", (10, 256, 256), 9))
 BV_INPUTS = ("balls + 0.2 % speckle", "30 % random")
@@ -302,7 +302,7 @@ def main():
     ap.add_argument("--step-timeout", type=float, default=300.0, help="seconds for each step (a child process of its own)")
     ap.add_argument("--out", default=None, help="also write the tables to this file (not profiles/cc_gpu_notes.md)")
     ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--by_value", action="store_true", help="the by-value tables (cc_value.hip: components of equal values, per-class winners)")
+    ap.add_argument("--by_value", action="store_true", help="the by-value tables (the ccv_* kernels of cc.hip: components of equal values, per-class winners)")
     ap.add_argument("--classes", type=int, default=None, help="with --by_value: this class count (2..256) for every volume instead of 3 / 3 / 4 / 9")
     args = ap.parse_args()
     if args.classes is not None and not (args.by_value and 2 <= args.classes <= 256):

@@ -10,7 +10,7 @@ Shapes: two offset balls as one class at 112x112x80 (the LA patch) and 192x160x8
 Medians of --reps runs after --warmup runs.  The two routes' results are compared before anything is timed (hd95 ==, asd to 1e-12).
 
 With --spacing SZ SY SX and / or --connectivity K (1..3) the same shapes are measured on the float64 record route instead
-(csrc/surface_sp.hip, surface_gpu.spaced_*): the host is metrics.binary with the same two arguments, "gpu kernels" is spaced_launch
+(csrc/surface.hip, surface_gpu.spaced_*): the host is metrics.binary with the same two arguments, "gpu kernels" is spaced_launch
 between two device events, "gpu wall" is spaced_metrics on device labels (kernels, the copy of the records, sort and finish), and one
 more column gives the unit-spacing integer route (surface_metrics from numpy arrays) on the same box for scale.  The routes are compared
 first (hd95 and asd within 1e-12).
