@@ -35,6 +35,17 @@ static inline bool arco_first_on_device(unsigned long long& mask) {
   return true;
 }
 
+// Launch Kernel with lds_bytes of dynamic LDS.  raise_to_bytes != 0: first raise the kernel's dynamic-LDS limit to that figure, once per
+// device (the mask is per instantiation; hipFuncSetAttribute is not legal inside a stream capture, so it never runs after warm-up).
+// The caller passes 0 where its launch stays under the 64 KB default.
+template <auto Kernel, typename... Args>
+static inline void arco_launch(dim3 grid, dim3 block, size_t lds_bytes, size_t raise_to_bytes, hipStream_t st, const Args&... args) {
+  static unsigned long long raised = 0;
+  if (raise_to_bytes && arco_first_on_device(raised))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)raise_to_bytes);
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
 // four consecutive channels of an activation row as fp32, from fp32 or f16 storage (the *_h entry points: f16 activation storage)

@@ -354,10 +354,7 @@ static int launch_fl(const IgemmArgs& a, hipStream_t st, int* q) {
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = a.Npad / G::BN;
   const int total = mblocks * b.n_nblocks, cus = conv_sp_cus();
-  auto kern = conv3d_fl_kernel<A_T, C_T>;
-  static unsigned long long attr_set = 0;
-  if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES); }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(512), G::LDS_BYTES, st, b);
+  arco_launch<conv3d_fl_kernel<A_T, C_T>>(dim3((unsigned)(total < cus ? total : cus)), dim3(512), G::LDS_BYTES, G::LDS_BYTES, st, b);
   return arco_launch_status();
 }
 
@@ -775,16 +772,10 @@ static int launch_fc(const IgemmArgs& a, hipStream_t st, int* q) {
   const int total = mblocks * b.n_nblocks, cus = conv_sp_cus();
   if (a.pro.mean) {           // consumer-side activation of the input
     if (a.pro.drop_mode != 0 || a.NB % (a.pro.groups > 1 ? a.pro.groups : 1) != 0) return ARCO_ERR_UNSUPPORTED;
-    auto kern = conv3d_fc_kernel<A_T, C_T, true, NCW>;
-    static unsigned long long attr_set = 0;
-    if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(512), lds, st, b);
+    arco_launch<conv3d_fc_kernel<A_T, C_T, true, NCW>>(dim3((unsigned)(total < cus ? total : cus)), dim3(512), lds, 160 * 1024, st, b);
     return arco_launch_status();
   }
-  auto kern = conv3d_fc_kernel<A_T, C_T, false, NCW>;
-  static unsigned long long attr_set = 0;
-  if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3((NCW + 4) * 64), lds, st, b);
+  arco_launch<conv3d_fc_kernel<A_T, C_T, false, NCW>>(dim3((unsigned)(total < cus ? total : cus)), dim3((NCW + 4) * 64), lds, 160 * 1024, st, b);
   return arco_launch_status();
 }
 template <int A_T, int C_T>

@@ -18,10 +18,11 @@
 //                    transposes and splits on the VALU).  Row strides are 8 x odd dwords: the eight rows a 32-lane half
 //                    reads land on eight distinct 8-bank groups.  The four waves of a workgroup take one 32-pixel K step of
 //                    a 128-pixel tile each and own ALL taps x sub-tiles (a tap's input fragment feeds CO_T MFMAs); partners
-//                    are summed once per launch.  Slabs [chunk][tap][CoutPad][CinPad] as in igemm.hip -> wgrad_reduce.
+//                    are summed once per launch.  Slabs [chunk][tap][CoutPad][CinPad] as in wgrad.hip -> wgrad_reduce.
 //   hconv_rw_kernel  the resident-weights form of hconv_kernel for the 16-channel full-resolution level (further down).
 //   cast kernels     the fp32 <-> f16 boundary of the V-Net (outputs up, gradients down with the loss scale).
 #include "sp_util.h"
+#include "wgrad.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -45,12 +46,8 @@ struct HGeom {
   // dwords per LDS row: 8 (3x3: 16 channels, no padding) / 24 (1x1: 32 channels + 8).  A ds_read_b128 is served in the lane groups
   // {0-3, 12-15, 20-27}, ...: eight rows r of one k-half and eight rows of the next half (+4 dwords) - conflict-free iff the row
   // stride is an EVEN number s of 4-dword slots (slots s*r are even, s*r + 1 odd, each set distinct mod 16); s = 3 (a 48-byte row)
-  // made 5 of every 16 lanes collide
-#ifdef ARCO_HCONV_ROWS_48_80      // A/B build: the padded rows measured first (5 of 16 lanes per ds_read_b128 group on a busy bank)
-  static constexpr int LDK = KC / 2 + 4;
-#else
+  // made 5 of every 16 lanes collide (the padded rows of KC / 2 + 4 dwords measured first: 48 / 80 bytes, both odd slot counts)
   static constexpr int LDK = KC == 16 ? 8 : 24;
-#endif
   static constexpr int TH = BM / 16;
   static constexpr int AROWS = TAPS == 9 ? (FLAT ? BM + 2 * HFLAT_WPMAX + 2 : (TH + 2) * 18) : BM;
   static constexpr int BROWS = TAPS * BN;
@@ -315,14 +312,11 @@ static int launch_hconv(const IgemmArgs& a, hipStream_t st, int* q) {
   size_t sh = (size_t)2 * G::BUF * 4;
   const size_t red = (size_t)2 * WM * BN * sizeof(float);
   if (sh < red) sh = red;
-  auto kern = hconv_kernel<TAPS, BM, BN, WM, WN, DEPTH, FLAT>;
-  static unsigned long long attr_set = 0;
-  if (sh > 64 * 1024 && arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); }
   IgemmArgs b = a;
   b.n_mblocks = mblocks;
   b.n_nblocks = (a.Npad + BN - 1) / BN;
   arco_note_route(TAPS * 1000000 + BM * 1000 + BN + (FLAT ? 500000 : 0));      // (2-D and 3-D tiles share ids: the call's taps tells them apart)
-  hipLaunchKernelGGL(kern, dim3((unsigned)(mblocks * b.n_nblocks)), dim3(256), sh, st, b);
+  arco_launch<hconv_kernel<TAPS, BM, BN, WM, WN, DEPTH, FLAT>>(dim3((unsigned)(mblocks * b.n_nblocks)), dim3(256), sh, sh > 64 * 1024 ? sh : 0, st, b);
   return arco_launch_status();
 }
 
@@ -562,14 +556,11 @@ static int launch_hconv_rw(const IgemmArgs& a, hipStream_t st, int* q) {
   if (S > a.D3) S = a.D3;
   const int nseg = (a.D3 + S - 1) / S;
   const long units = cols * nseg;
-  auto kern = hconv_rw_kernel<NC, C_T, TH>;
-  static unsigned long long attr_set = 0;
-  if (G::LDS_BYTES > 64 * 1024 && arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES); }
   IgemmArgs b = a;
   b.n_mblocks = (int)(a.NB * tiles);
   const long grid = slots < units ? slots : units;
   arco_note_route(9 * 1000000 + 400000 + TH * 1000 + C_T * 16);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NT), G::LDS_BYTES, st, b, S, nseg);
+  arco_launch<hconv_rw_kernel<NC, C_T, TH>>(dim3((unsigned)grid), dim3(G::NT), G::LDS_BYTES, G::LDS_BYTES > 64 * 1024 ? G::LDS_BYTES : 0, st, b, S, nseg);
   return arco_launch_status();
 }
 
@@ -834,11 +825,8 @@ static int launch_hfc(const IgemmArgs& a, hipStream_t st, int* q) {
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = a.Npad / G::BN;
   const int total = mblocks * b.n_nblocks, cus = conv_sp_cus();
-  auto kern = hconv_fc_kernel<A_T, C_T>;
-  static unsigned long long attr_set = 0;
-  if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
   arco_note_route(9260000 + A_T * 1000 + G::BN);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(512), lds, st, b);
+  arco_launch<hconv_fc_kernel<A_T, C_T>>(dim3((unsigned)(total < cus ? total : cus)), dim3(512), lds, 160 * 1024, st, b);
   return arco_launch_status();
 }
 
@@ -1189,14 +1177,11 @@ static void launch_hwgrad(const HWgradArgs& a, dim3 grid, hipStream_t st) {
   size_t sh = (size_t)(128 * RSZ + XR * RSX) * 4;
   const size_t rd = (size_t)4 * CO_T * CI_T * 4 * 64 * 4;
   if (sh < rd) sh = rd;
-  auto kern = hwgrad_kernel<CO_T, CI_T, NT>;
-  static unsigned long long attr_set = 0;
-  if (sh > 64 * 1024 && arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh); }
-  hipLaunchKernelGGL(kern, grid, dim3(256), sh, st, a);
+  arco_launch<hwgrad_kernel<CO_T, CI_T, NT>>(grid, dim3(256), sh, sh > 64 * 1024 ? sh : 0, st, a);
 }
 
 // the slabs of the weight gradient from f16 dZ / X into ws (sized by arco_wgrad_ws_floats, same slab reservation as the fp32 kernels);
-// tile, grid and slab count are wgrad_plan's (igemm.hip), the caller sums the slabs
+// tile, grid and slab count are wgrad_plan's (wgrad.hip), the caller sums the slabs
 int hwgrad_dispatch(const void* dZ, long ld_dz, int Cout, const void* in, long ld_in, int Cin, int taps, int NB, int D3, int H, int W,
                     float* ws, const WgradPlan& p, hipStream_t st) {
   if (p.family != WG_F_HGRAD) return ARCO_ERR_UNSUPPORTED;

@@ -755,16 +755,10 @@ static int launch_rw(const IgemmArgs& a, hipStream_t st, int* q) {
   const int cus = conv_sp_cus();
   if (a.pro.mean) {           // consumer-side activation of the input (the block's first BatchNorm + LeakyReLU + dropout)
     if ((a.K & 15) != 0) return ARCO_ERR_UNSUPPORTED;
-    auto kern = conv3x3_rw_kernel<A_T, C_T, true, NCW>;
-    static unsigned long long attr_set = 0;
-    if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(mblocks < cus ? mblocks : cus)), dim3((NCW + 4) * 64), lds, st, b);
+    arco_launch<conv3x3_rw_kernel<A_T, C_T, true, NCW>>(dim3((unsigned)(mblocks < cus ? mblocks : cus)), dim3((NCW + 4) * 64), lds, 160 * 1024, st, b);
     return arco_launch_status();
   }
-  auto kern = conv3x3_rw_kernel<A_T, C_T, false, NCW>;
-  static unsigned long long attr_set = 0;
-  if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(mblocks < cus ? mblocks : cus)), dim3((NCW + 4) * 64), lds, st, b);
+  arco_launch<conv3x3_rw_kernel<A_T, C_T, false, NCW>>(dim3((unsigned)(mblocks < cus ? mblocks : cus)), dim3((NCW + 4) * 64), lds, 160 * 1024, st, b);
   return arco_launch_status();
 }
 
@@ -779,16 +773,10 @@ static int launch_sp(const IgemmArgs& a, hipStream_t st, int* q) {
   b.n_mblocks = mblocks; b.n_nblocks = a.Npad / G::BN;
   const int total = mblocks * b.n_nblocks, cus = conv_sp_cus();
   if (a.pro.mean) {           // consumer-side activation of the input (the block's first BatchNorm + LeakyReLU + dropout)
-    auto kern = conv3x3_sp_kernel<A_T, C_T, true>;
-    static unsigned long long attr_set = 0;
-    if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES); }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(512), G::LDS_BYTES, st, b);
+    arco_launch<conv3x3_sp_kernel<A_T, C_T, true>>(dim3((unsigned)(total < cus ? total : cus)), dim3(512), G::LDS_BYTES, G::LDS_BYTES, st, b);
     return arco_launch_status();
   }
-  auto kern = conv3x3_sp_kernel<A_T, C_T>;
-  static unsigned long long attr_set = 0;
-  if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES); }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(total < cus ? total : cus)), dim3(512), G::LDS_BYTES, st, b);
+  arco_launch<conv3x3_sp_kernel<A_T, C_T>>(dim3((unsigned)(total < cus ? total : cus)), dim3(512), G::LDS_BYTES, G::LDS_BYTES, st, b);
   return arco_launch_status();
 }
 
@@ -966,12 +954,10 @@ int conv3d_rw_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
   if (S > a.D3) S = a.D3;
   const int nseg = (a.D3 + S - 1) / S;
   const long units = cols * nseg;
-  static unsigned long long attr_set = 0;
-  if (arco_first_on_device(attr_set)) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_rw16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES); }
   IgemmArgs b = a;
   b.n_mblocks = (int)(a.NB * tiles);
   arco_note_route(9 * 1000000 + 450000 + 16);
-  hipLaunchKernelGGL(conv3d_rw16_kernel, dim3((unsigned)(slots < units ? slots : units)), dim3(G::NT), G::LDS_BYTES, st, b, S, nseg);
+  arco_launch<conv3d_rw16_kernel>(dim3((unsigned)(slots < units ? slots : units)), dim3(G::NT), G::LDS_BYTES, G::LDS_BYTES, st, b, S, nseg);
   return arco_launch_status();
 }
 

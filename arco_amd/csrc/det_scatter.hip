@@ -15,7 +15,8 @@
 //
 // The accumulator is a persistent int64 buffer, zero by invariant: finish converts the touched rows into the fp32 destination
 // (overwriting: the destination rows hold nothing else), clear re-zeroes them.
-#include "igemm_args.h"
+#include "interp.h"
+#include "split_bf16.h"
 
 #define DET_BITS 44
 

@@ -5,7 +5,7 @@
 // flat-buffer SGD-Nesterov and EMA (train_arco_2d.py:248,306-308,432; model_2D.py:176-182).
 // All kernels: float4 per lane along the channel axis, grid-stride over pixels.
 #include "common.h"
-#include "igemm_args.h"
+#include "interp.h"
 
 // (pcg_hash / drop_keep: common.h - the consumer-side activation of the convolution loaders draws the same masks)
 

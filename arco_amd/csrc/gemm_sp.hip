@@ -18,6 +18,8 @@
 // LDS: 2 x (64 + 256) rows x 56 dwords = 143,360 bytes.  Shapes taken (gemm_sp_dispatch): split-bf16 mode, K % 4 == 0, aligned
 // rows, no BN statistics / split-K / batching, enough tiles for every CU; everything else stays on igemm_kernel.
 #include "igemm_args.h"
+#include "interp.h"
+#include "split_bf16.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -418,16 +420,11 @@ int gemm_sp_dispatch(const IgemmArgs& a, hipStream_t st, int* q) {
     (void)hipGetDevice(&dev);
     n_cu = hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256;
   }
-  static unsigned long long attr_set = 0;       // (one bit per device: a process may drive several, common.h)
-  if (arco_first_on_device(attr_set)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_sp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF_DW * 4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_sp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BUF_DW * 4);
-  }
   IgemmArgs b = a;
   b.n_mblocks = mblocks; b.n_nblocks = nblocks;
   const int grid = (int)(tiles < n_cu ? tiles : n_cu);
   arco_note_route(1000000 + BM * 1000 + BN + (a.Rup ? 450000 : 400000));      // gemm_sp_kernel<false> 1464256, <true> (fused upsample) 1514256
-  if (a.Rup) hipLaunchKernelGGL(gemm_sp_kernel<true>, dim3(grid), dim3(512), 2 * BUF_DW * 4, st, b);
-  else hipLaunchKernelGGL(gemm_sp_kernel<false>, dim3(grid), dim3(512), 2 * BUF_DW * 4, st, b);
+  if (a.Rup) arco_launch<gemm_sp_kernel<true>>(dim3(grid), dim3(512), 2 * BUF_DW * 4, 2 * BUF_DW * 4, st, b);
+  else arco_launch<gemm_sp_kernel<false>>(dim3(grid), dim3(512), 2 * BUF_DW * 4, 2 * BUF_DW * 4, st, b);
   return arco_launch_status();
 }

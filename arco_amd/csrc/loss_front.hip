@@ -1151,12 +1151,8 @@ int arco_nce_fused(const float* S, long ld, const int* lens, const int* prow, in
   for (int e = 0; e < E; ++e) { ARCO_CHECK_ARG(t.len[e] > 0 && t.len[e] <= ld); if (t.len[e] > Lmax) Lmax = t.len[e]; }
   const size_t sh = (size_t)((Lmax + 1) / 2) * sizeof(uint32_t);
   ARCO_CHECK_ARG(sh <= (size_t)(160 * 1024 - 512));
-  static unsigned long long attr_set = 0;
-  if (sh > 48 * 1024 && arco_first_on_device(attr_set)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(infonce_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-  }
-  hipLaunchKernelGGL(infonce_fused_kernel, dim3((unsigned)Q, (unsigned)E), dim3(256), sh, as_stream(stream), S, ld, t, idx_all,
-                     idx_off, idx_stride, Q, Nn, An, Pn_all, Dp, 1.0f / temp, W, gpos, loss_q);
+  arco_launch<infonce_fused_kernel>(dim3((unsigned)Q, (unsigned)E), dim3(256), sh, sh > 48 * 1024 ? 160 * 1024 - 512 : 0, as_stream(stream), S, ld, t,
+                                    idx_all, idx_off, idx_stride, Q, Nn, An, Pn_all, Dp, 1.0f / temp, W, gpos, loss_q);
   return arco_launch_status();
 }
 int arco_nce_anchor_grad(const float* G, const float* An, const float* Pn_all, const int* prow, int E, const float* gpos,
@@ -1179,13 +1175,10 @@ int arco_nce_prep(const float* A, long n_a, const float* P, long n_p, int D, int
                  n_p > 0 && D > 0 && Dp >= D && Q > 0 && Nn > 0 && Nn < 65536 && Lp > 0 && (Lp & 15) == 0 && Lp <= arco_nce_max_len());
   for (int e = 0; e < E; ++e) ARCO_CHECK_ARG(t.len[e] > 0 && t.len[e] <= Lp);
   const size_t sh = (size_t)Lp * 2;
-  static unsigned long long attr_set = 0;
-  if (sh > 48 * 1024 && arco_first_on_device(attr_set))
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nce_prep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
   const long blocks = (n_a + n_p + 3) / 4 + n_a;
   NceIdx ix{idx_all, idx_off, idx_stride};
-  hipLaunchKernelGGL(nce_prep_kernel, dim3((unsigned)blocks), dim3(256), sh, as_stream(stream), A, n_a, P, n_p, D, Dp, eps, An, invA, Pn, t, ix,
-                     Q, Nn, Lp, reinterpret_cast<unsigned short*>(M));
+  arco_launch<nce_prep_kernel>(dim3((unsigned)blocks), dim3(256), sh, sh > 48 * 1024 ? 160 * 1024 - 512 : 0, as_stream(stream), A, n_a, P, n_p, D, Dp,
+                               eps, An, invA, Pn, t, ix, Q, Nn, Lp, reinterpret_cast<unsigned short*>(M));
   return arco_launch_status();
 }
 long arco_nce_score_ltiles(long Lp) { return (Lp + NS_BN - 1) / NS_BN; }

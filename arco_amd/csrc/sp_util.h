@@ -2,6 +2,7 @@
 // types, counted waits, DPP row sums, the asm MFMA forms with pinned accumulators, the CU count of the device.
 #pragma once
 #include "igemm_args.h"
+#include "split_bf16.h"
 #include <stdlib.h>
 #include <type_traits>
 

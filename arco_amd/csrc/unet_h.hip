@@ -15,6 +15,8 @@
 // The VALU kernels move 8 channels (16 bytes) per lane.
 #include <initializer_list>
 #include "sp_util.h"
+#include "interp.h"
+#include "wgrad.h"
 
 typedef _Float16 uh8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));

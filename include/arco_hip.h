@@ -123,7 +123,10 @@ int arco_sum_scale(const float* x, int n, float scale, float* out, int accumulat
    per 32 k, fp32-accurate) and therefore takes the split-packed weights (arco_pack_conv_weight mode | 2); else 0      */
 int arco_conv_split_ok(int taps, int NB, int H, int W, int Cin, int Cout, long ld_in);
 /* ---- N1-N4  convolutions on the fp32 matrix cores (nn.Conv2d 3x3 / 1x1: unetWithArgs.py:36-44,72,139;
- *      model_2D.py:25-33; train_arco_2d.py:231-234).  Wp = packed weights [taps][ceil16(N)][ceil16(K)].    */
+ *      model_2D.py:25-33; train_arco_2d.py:231-234).  Wp = packed weights [taps][ceil16(N)][ceil16(K)].
+ *      Sources: csrc/igemm.hip (forward / data gradient, weight packing, the shape queries), csrc/wgrad.hip (weight and bias
+ *      gradients: arco_conv_wgrad, arco_conv3d_wgrad(_pro), arco_wgrad_*, arco_colsum(_h)), with the pipelined kernels of
+ *      conv_sp.hip, conv3d_fl.hip and gemm_sp.hip behind the same entry points.                                */
 int arco_pack_conv_weight(const float* W, int Cout, int Cin, int taps, int mode, float* Wp, void* stream);
 /* all conv weights of a model in ONE launch: `desc` = device array of records {const float* src; float* dst;
  * int Cout, Cin, taps, mode, Npad, Kpad; long first;} (arco_pack_desc_bytes() bytes each).

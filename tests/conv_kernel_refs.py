@@ -30,7 +30,7 @@ Bounds of the wide kind (u = 2^-24, gamma(n) = n u / (1 - n u); tol = gamma(n) S
          2 taps K + 2 (bias, residual in the epilogue).  Zero padding adds exact zeros.
   mfma3  the split-bf16 kernels (mma 3: igemm_kernel, conv_sp.hip, gemm_sp.hip, conv3d_fl.hip): a product of two bf16 terms has 16
          bits and is exact; every kept product is one accumulation: n = 6 taps K + 2.  The three dropped products are bounded by
-         (2^-23 + 2^-24) |x||w| (igemm_args.h).  Rigorous and loose at large K; the measured 3e-6 S is what binds there."""
+         (2^-23 + 2^-24) |x||w| (split_bf16.h).  Rigorous and loose at large K; the measured 3e-6 S is what binds there."""
 import functools
 import math
 
@@ -416,7 +416,7 @@ def stats_tol(c, d, groups):
 
 
 # ======================================================================================================================================
-# the two split rules of igemm_args.h and the fp32 emulation of the wide kind
+# the two split rules (split_bf16.h: the activation split; igemm.hip store_split3: the all-round-to-nearest weight pack) and the fp32 emulation of the wide kind
 # ======================================================================================================================================
 def bf16_rne(v):
     """float32 array -> the nearest bf16 value (ties to even), as float32"""

@@ -7,7 +7,7 @@ take the GPU file's device buffers and the CPU file's host buffers alike.
 Every case is seeded, computed once (functools.lru_cache) and never modified.  Every reference is float64 / int64 computed from the
 SAME fp32 (or f16) values the kernel reads.  u = 2^-24; gamma(k) = k u / (1 - k u).
 
-The align_corners index arithmetic (igemm_args.h ac_src) is restated in numpy float32 (ac_axis32: one IEEE division, one
+The align_corners index arithmetic (interp.h ac_src) is restated in numpy float32 (ac_axis32: one IEEE division, one
 multiplication, a truncation, a subtraction; contraction is off in ac_src) and, separately, in exact integer arithmetic
 (ac_axis_exact): the two are compared where the kernels' indices and weights are outputs."""
 import functools

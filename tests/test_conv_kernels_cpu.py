@@ -5,7 +5,7 @@
   * the input conditions of every case and kind: the 2^24 bit budget and the two-term operands of the fixed kind, the spacing of the
     impulses, one product per output in both impulse kinds, S > 0 wherever the reference is not zero, and the float64 reference
     exactly representable in fp32 for the exact kinds;
-  * the wide kind emulated in fp32 (both split rules of igemm_args.h, the six kept products formed exactly, one fixed accumulation
+  * the wide kind emulated in fp32 (both split rules: split_bf16.h and the weight pack of igemm.hip, the six kept products formed exactly, one fixed accumulation
     order) stays inside the same bounds; the ratios are printed and recorded in the GPU file's docstring;
   * each comparison helper rejects a planted error: one tap mirrored, one border column not zero-padded, channels k and k + 16
     swapped, the plane-1 term of one weight dropped, the bias added twice on one tile, one slab counted in the wrong group;
@@ -62,6 +62,28 @@ def test_case_reaches_its_route(L, c):
         npad, nb = R.ceil_to(N, 16), -(-R.ceil_to(N, 16) // 256)
         assert c["gsp"] and c["mma"] == 3 and K % 4 == 0 and N % 4 == 0 and c["ld_in"] % 4 == 0 and c["ld_out"] % 4 == 0 and c["ld_res"] % 4 == 0
         assert npad >= 64 and R.ceil_to(K, 32) >= 32 and nb * 256 - npad <= nb * 256 // 5 and c["route"] == 1464256
+
+
+def test_plain_queries_are_the_mma0_case_of_their_twins(L):
+    """arco_conv_mblocks / arco_conv_config answer what arco_conv_mblocks_mma / arco_conv_config_mma answer for mma = 0 (one shape record
+    and one route behind all four), and arco_conv_config fills *kc_depth_db whenever it names a kernel.  Host only: 384 shapes."""
+    lib = L.load()
+    seen = 0
+    for taps in (1, 9, 27):
+        for nb in (1, 8):
+            for h, w in ((7, 5), (16, 16), (33, 45), (64, 64)):
+                for cin, cout in ((1, 16), (16, 16), (20, 48), (64, 128)):
+                    for ld in (cin, cin + 4):
+                        shape = (taps, nb, h, w, cin, cout, ld)
+                        kdd = ctypes.c_int(-1)
+                        cfg = lib.arco_conv_config(*shape, ctypes.byref(kdd))
+                        assert cfg == lib.arco_conv_config_mma(*shape, 0), shape
+                        if cfg > 0:
+                            assert kdd.value > 0, (shape, cfg)
+                            seen += 1
+                        for groups in (1, 2):
+                            assert lib.arco_conv_mblocks(*shape, groups) == lib.arco_conv_mblocks_mma(*shape, groups, 0), (shape, groups)
+    assert seen > 0
 
 
 def test_refused_width_of_the_pipelined_gemm_is_what_the_dispatcher_says():

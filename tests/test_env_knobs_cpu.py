@@ -23,6 +23,10 @@ RETIRED = {
     # process flags that keep their setter (arco_conv_sp_set, arco_conv3d_fl_set, arco_gemm_sp_set) and lose the environment read
     "ARCO_CONV_SP": "arco_conv_sp_set", "ARCO_CONV3D_FL": "arco_conv3d_fl_set", "ARCO_GEMM_SP": "arco_gemm_sp_set",
     "ARCO_GEMM_SP_TILES": "arco_gemm_sp_set",
+    # compile-time switches (-D...) of decided experiments; the findings stand in the comments of split_bf16.h, interp.h, wgrad.hip, conv_h.hip
+    "ARCO_AC_FAST": "contraction off in ac_src", "ARCO_SPLIT_TRUNC0": "first term rounded to nearest", "ARCO_SPLIT_RNE": "truncated second term",
+    "ARCO_SPLIT_PACKED": "element-wise form gone with the all-RNE split", "ARCO_HCONV_ROWS_48_80": "rows of 8 / 24 dwords",
+    "ARCO_WG_SWZ": "swizzled rows (constexpr WG_SWZ)", "ARCO_WG_CSZ": "72 (constexpr WG_CSZ)", "ARCO_WG_CSX": "136 (constexpr WG_CSX)",
 }
 
 

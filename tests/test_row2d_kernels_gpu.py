@@ -19,7 +19,7 @@ and every product-sum fused), the GPU's the largest printed by this file on an M
 The bit comparisons found one disagreement, fixed in the kernels: written as the plain expression hy (hx v00 + lx v01) + ly (hx v10 +
 lx v11), the dense resize, the gather and the 4-way lerp compiled to three different chains of multiplies and fused multiply-adds -
 the gather's rows differed from the dense resize's in the last bit on 0.5 % of the elements, the lerp's from the gather's on 14 % -
-although each was far inside the float64 bound.  All three now evaluate bl_blend1 (csrc/igemm_args.h), one explicit chain."""
+although each was far inside the float64 bound.  All three now evaluate bl_blend1 (csrc/interp.h), one explicit chain."""
 import ctypes
 
 import pytest

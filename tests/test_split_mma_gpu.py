@@ -207,7 +207,7 @@ def test_pipelined_gemm_is_bit_identical_to_the_implicit_gemm_kernel():
                                    dict(nb=1, c=496, sp=(64, 64), k=1)])
 def test_activation_split_is_an_exact_decomposition_through_the_kernels(shape):
     """The loaders split every activation into three bf16 terms (round 6: the first by round-to-nearest, the second by truncation, the
-    third the exact rest - igemm_args.h).  x = t0 + t1 + t2 must hold bit for bit: a convolution whose weights are the identity on the
+    third the exact rest - split_bf16.h).  x = t0 + t1 + t2 must hold bit for bit: a convolution whose weights are the identity on the
     centre tap (1, 0, 0 in the weight terms) accumulates exactly (t2 + t1) + t0 per output and has to hand the input back unchanged -
     on six decades of magnitudes, exact zeros and negative values, through the pipelined 2-D kernels (resident weights, LDS-DMA ring),
     the 3x3x3 flat-tile and plane-ring kernels and the wide 1x1 GEMM."""

@@ -15,7 +15,7 @@ def _round(t, mode):
 
 
 def _ac_src(n_out, n_in):
-    """ac_src of csrc/igemm_args.h in fp32: src = scale * index, i0 = (int)src clamped, i1 = i0 + 1 clamped, l1 = src - i0."""
+    """ac_src of csrc/interp.h in fp32: src = scale * index, i0 = (int)src clamped, i1 = i0 + 1 clamped, l1 = src - i0."""
     one = torch.ones((), dtype=torch.float32)
     scale = (one * (n_in - 1)) / (one * (n_out - 1)) if n_out > 1 else torch.zeros((), dtype=torch.float32)
     src = scale * torch.arange(n_out, dtype=torch.float32)
