@@ -50,6 +50,8 @@ _SIGS = {
     "arco_cc_value_largest": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P],
     "arco_zoom_nearest2d": [_P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _I, _P, _P],
     "arco_argmax_zoom_back2d": [_P, _L, _I, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P],
+    "arco_spline_prefilter2d": [_P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _P],
+    "arco_zoom_cubic2d": [_P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P],
     "arco_mix_unsup": [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
     "arco_label_presence": [_P, _I, _L, _P, _P],
     "arco_window_accumulate": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],

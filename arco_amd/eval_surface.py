@@ -11,6 +11,11 @@ predict_volume and test_single_volume take `zoom="host"` (default: test_2D.predi
 slice) or `zoom="gpu"` (utils/zoom_gpu.py: the volume is uploaded once, resampled to the patch on the device, and the arg-max map is
 resampled back by the kernel that takes the arg-max - the same label map, bit for bit, as a device tensor; in test_single_volume with
 surface="gpu" only, where it goes on to the overlap counts and the surface kernels without leaving the device).
+Both also take `order=0` (default: every path exactly as without the keyword) or `order=3`, the route of the reference's
+test.py:116-135: a slice whose size differs from the patch goes to the patch by the cubic-spline zoom (scipy.ndimage.zoom(order=3) on
+zoom="host"; zoom_gpu.zoom_cubic, its float64 prefilter and interpolation as HIP kernels, on zoom="gpu"), a slice of patch size is passed
+as it is, and the arg-max map goes back by order 0 as before.  On zoom="gpu" an order-3 volume must be float32 (the cast does not
+commute with the spline; ValueError otherwise).  Any other order is a ValueError before any GPU work.
 The metric functions, test_single_volume and test_all_case also take metrics.binary's `voxelspacing=None, connectivity=1` (medpy's
 meaning: None is 1.0, a number is broadcast, a sequence has one entry per axis of the scored map - three for the [S, X, Y] volume of
 test_single_volume; connectivity 1..ndim).  With both at their defaults every function takes the path it took without them.  Otherwise
@@ -113,15 +118,49 @@ def calculate_metric_percase_2d(pred, gt, surface="host", voxelspacing=None, con
 
 
 @torch.no_grad()
-def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0", zoom="host"):
+def _predict_volume_host(image, net, patch_size, batch=32, device="cuda:0", order=0):
+    """The host route's label map, an int64 numpy array.  order=0 is a plain call of test_2D.predict_volume.  order=3 restates its loop
+    (that module stays as it is) with the reference's test.py:116-135 in place of the two zoom calls: a slice goes to the patch by
+    scipy's zoom(order=3) only when its size differs from the patch - a slice of patch size is passed as it is, a cubic zoom by 1.0 is
+    not the identity in bits - and the arg-max map comes back by order 0 under the same condition."""
+    if order == 0:
+        return _t2d.predict_volume(image, net, patch_size, batch=batch, device=device)
+    from scipy.ndimage import zoom
+    image = np.asarray(image)
+    S, x, y = image.shape
+    as_is = (x, y) == (patch_size[0], patch_size[1])
+    zoomed = image if as_is else np.stack([zoom(image[i], (patch_size[0] / x, patch_size[1] / y), order=3) for i in range(S)])
+    prediction = np.zeros((S, x, y), dtype=np.int64)
+    was_training = net.training
+    net.eval()
+    for s0 in range(0, S, batch):
+        inp = torch.from_numpy(np.ascontiguousarray(zoomed[s0:s0 + batch])).unsqueeze(1).float().to(device)
+        out = _glue.softmax_max(net(inp)[0])[1].cpu().numpy()
+        for i in range(out.shape[0]):
+            prediction[s0 + i] = out[i] if as_is else zoom(out[i], (x / patch_size[0], y / patch_size[1]), order=0)
+    if was_training:
+        net.train()
+    return prediction
+
+
+@torch.no_grad()
+def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0", zoom="host", order=0):
     """Label map of a [S, X, Y] volume.  zoom="host": test_2D.predict_volume, an int64 numpy array.  zoom="gpu": the same label map as an
     int64 tensor ON THE DEVICE - the volume is uploaded once as float32 (nearest sampling and zero fill commute with the cast),
     zoom_gpu.zoom_nearest takes every slice to the patch, the eval-mode net runs in the same batches, and zoom_gpu.argmax_zoom_back
     turns each batch of logits into labels of the slices' own size.  ValueError, before any launch, when scipy's round trip would not
-    come back to (X, Y) (the host route fails on its assignment there)."""
-    if _zoom_gpu.check_zoom(zoom) == "host":
-        return _t2d.predict_volume(image, net, patch_size, batch=batch, device=device)
+    come back to (X, Y) (the host route fails on its assignment there).
+    order=3: the slices go to the patch by the cubic-spline zoom where their size differs from the patch (test.py:123-124) and as they
+    are where it does not - scipy's zoom(order=3) on the host, zoom_gpu.zoom_cubic on the device, where the volume must be
+    float32 -; the way back is unchanged (at patch size argmax_zoom_back samples every pixel: the arg-max map itself)."""
+    _zoom_gpu.check_zoom(zoom)
+    _zoom_gpu.check_order(order)
+    if zoom == "host":
+        return _predict_volume_host(image, net, patch_size, batch=batch, device=device, order=order)
     image = np.asarray(image)
+    if order == 3 and image.dtype != np.float32:
+        raise ValueError("zoom=\"gpu\", order=3 takes a float32 volume (the cast does not commute with the spline): cast it with "
+                         f"image.astype(np.float32) first, got {image.dtype}")
     S, x, y = image.shape
     Z0, Z1 = (_zoom_gpu.zoomed_size(n, p)[0] for n, p in zip((x, y), patch_size))      # scipy's int(round(n * (p / n)))
     back = tuple(int(round(Z * (n / p))) for Z, n, p in zip((Z0, Z1), (x, y), patch_size))
@@ -130,7 +169,10 @@ def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0",
     if back != (x, y):
         raise ValueError(f"zoom(order=0) of a {(Z0, Z1)} map by {(x / patch_size[0], y / patch_size[1])} has shape {back}, not {(x, y)}")
     vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
-    zoomed = _zoom_gpu.zoom_nearest(vol, (Z0, Z1))
+    if order == 0:
+        zoomed = _zoom_gpu.zoom_nearest(vol, (Z0, Z1))
+    else:
+        zoomed = vol if (x, y) == (patch_size[0], patch_size[1]) else _zoom_gpu.zoom_cubic(vol, (Z0, Z1))
     prediction = torch.empty((S, x, y), dtype=torch.int64, device=vol.device)
     was_training = net.training
     net.eval()
@@ -144,26 +186,28 @@ def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0",
 
 @torch.no_grad()
 def test_single_volume(image, label, net, classes, patch_size=(256, 256), device="cuda:0", surface="host", zoom="host",
-                       voxelspacing=None, connectivity=1, nms=0, cc="host"):
+                       voxelspacing=None, connectivity=1, nms=0, cc="host", order=0):
     """test_2D.test_single_volume; with surface="gpu" the surface metrics of all classes come from one call on the label volumes that
     are on the device for the overlap counts already.  zoom="gpu" (with surface="gpu" only) is the device-resident case: the label map
     of predict_volume(zoom="gpu") goes to the overlap counts and the surface kernels as the device tensor it is.  Every class is scored on
     the [S, X, Y] volume as the 3-D object it is, so a voxelspacing has three entries.
     nms=1 keeps, before anything is counted or measured, only the largest component of every class of the [S, X, Y] prediction (the 3-D
     object it is, full connectivity): cc="host" (default) through cc_host.keep_largest_per_class on the host map, cc="gpu" (with
-    surface="gpu" only) through cc_gpu.largest_per_class - with zoom="gpu" the label map then never leaves the device."""
+    surface="gpu" only) through cc_gpu.largest_per_class - with zoom="gpu" the label map then never leaves the device.
+    order=3 is predict_volume's: the cubic-spline zoom of the slices to the patch on either route, everything after it unchanged."""
     _surface_gpu.check_route(surface)
+    _zoom_gpu.check_order(order)
     if _zoom_gpu.check_zoom(zoom) == "gpu" and surface != "gpu":
         raise ValueError('zoom="gpu" is the device-resident head of surface="gpu"; got surface=%r' % (surface,))
     if _cc_gpu.check_cc(cc) == "gpu" and surface != "gpu":
         raise ValueError('cc="gpu" is the device-resident tail of surface="gpu"; got surface=%r' % (surface,))
     unit = _unit(voxelspacing, connectivity)
-    if surface == "host" and unit and not nms:
+    if surface == "host" and unit and not nms and order == 0:
         return _t2d.test_single_volume(image, label, net, classes, patch_size, device=device)
     if not unit:
         _surface_gpu.check_spaced_args(voxelspacing, connectivity, 3)
     if surface == "host":
-        prediction = _t2d.predict_volume(image, net, patch_size, device=device)
+        prediction = _predict_volume_host(image, net, patch_size, device=device, order=order)
         if nms:
             prediction = _cc_host.keep_largest_per_class(prediction)
         cnt = _t2d.overlap_counts(torch.from_numpy(prediction).to(device), torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device),
@@ -171,11 +215,11 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), device
         return _metric_list(cnt, classes, lambda c: (_binary.hd95(prediction == c, label == c, voxelspacing, connectivity),
                                                      _binary.asd(prediction == c, label == c, voxelspacing, connectivity)))
     if zoom == "gpu":
-        pred_d = predict_volume(image, net, patch_size, device=device, zoom="gpu")
+        pred_d = predict_volume(image, net, patch_size, device=device, zoom="gpu", order=order)
         if nms and cc == "host":
             pred_d = torch.from_numpy(_cc_host.keep_largest_per_class(pred_d.cpu().numpy())).to(device)
     else:
-        prediction = _t2d.predict_volume(image, net, patch_size, device=device)
+        prediction = _predict_volume_host(image, net, patch_size, device=device, order=order)
         if nms and cc == "host":
             prediction = _cc_host.keep_largest_per_class(prediction)
         pred_d = torch.from_numpy(prediction).to(device)

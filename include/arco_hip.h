@@ -534,6 +534,22 @@ int arco_zoom_nearest2d(const void* src, int S, int n0, int n1, int N0, int N1, 
                         void* stream);
 int arco_argmax_zoom_back2d(const float* X, long ld, int C, int n, int P0, int P1, int N0, int N1, double z0, double z1, int64_t* out,
                             void* stream);
+/* ---- V  zoom(order=3) of 2-D evaluation (the reference's test.py:124; csrc/zoom.hip, arco_amd/utils/zoom_gpu.py):
+ *      scipy.ndimage.zoom(a, f, order=3) with scipy's defaults (mode='constant', cval=0, prefilter=True, grid_mode=False) of float32
+ *      slices, as two steps in float64 without contraction, every operation in the order tests/zoom_cubic_kernel_refs.py restates.
+ *      arco_spline_prefilter2d: src float32 [S][n0][n1] -> out float64 B-spline coefficients [S][n0][n1].  Along every line of n points,
+ *      axis 0 (axes & 1) then axis 1 (axes & 2; alone it filters `out` in place and reads no `src`): the gain, the causal initial sum
+ *      over the whole line (mirror boundary), the causal and the anticausal recursion, strictly in sequence.  z = sqrt(3) - 2,
+ *      gain = (1 - z)(1 - 1 / z), zn0 = z^(n0 - 1), zn1 = z^(n1 - 1) are computed by the caller in float64.  ARCO_ERR_ARG before
+ *      anything is launched for: a null pointer, S < 1, n0 / n1 < 2, axes outside 1..3, a z / gain / zn that is not finite.
+ *      arco_zoom_cubic2d: coef [S][n0][n1] -> out float32 [S][N0][N1].  Output index o of an axis samples cc = (double)o * z,
+ *      z = (n_in - 1) / (n_out - 1) from the caller; the output is 0 where !(0 <= cc <= n_in - 1), else the sum over the 4 x 4 taps
+ *      floor(cc) - 1 .. + 2 (mirrored into [0, n_in - 1]) of coef * w_axis0 * w_axis1, cast to float32.  Any alignment of `out`.
+ *      ARCO_ERR_ARG before anything is launched for: a null pointer, S < 1, n0 / n1 < 2 or > 2^30, N0 / N1 < 2, a z that is negative
+ *      or not finite.                                                                                                              */
+int arco_spline_prefilter2d(const float* src, int S, int n0, int n1, double z, double gain, double zn0, double zn1, int axes, double* out,
+                            void* stream);
+int arco_zoom_cubic2d(const double* coef, int S, int n0, int n1, int N0, int N1, double z0, double z1, float* out, void* stream);
 /* ---- A  mixing strategies of the unlabeled stream (augment.py:284-313 generate_unsup_data, masks :230-252; volumes
  *      augment_3d.py:182-257).  desc_host[B][8] = {y0, y1, x0, x1, z0, z1, sel_lo, sel_hi} in HOST memory (the host
  *      draws it; it travels in the kernel arguments); Z = 1 in 2-D; mode 0 cutmix, 1 cutout, 2 classmix; data NC[spatial] */

@@ -9,11 +9,14 @@ image of noisy discs and labels of the same discs):
   kernels  zoom_gpu.zoom_nearest of the float32 volume to the patch and zoom_gpu.argmax_zoom_back of the logits to the slices' size,
            each between two device events; next to them scipy's zoom over the same slices on the host
 Medians after warm-up.  Before anything is timed the two routes are compared: the same label map (array_equal) and the same metrics (==).
+--order 3 adds, per volume, the same case with the cubic-spline zoom of the slices (order=3, the reference's test.py:116-135) on the
+host route and on the gpu route, next to the order-0 gpu route of the same process, and the three kernels of zoom_gpu.zoom_cubic alone
+(the two prefilter passes and the interpolation) next to the bytes each must move and scipy's zoom(order=3) of the same slices.
 
 Every step runs in a child process of its own under --step-timeout seconds; the first step that fails or runs out of time ends the
 run (nothing more is started on the GPU after it).
 
-  python tools/eval2d_bench.py [--reps 10 --warmup 3 --kernel-reps 50 --step-timeout 300] [--out eval2d_bench_table.md]
+  python tools/eval2d_bench.py [--order 3] [--reps 10 --warmup 3 --kernel-reps 50 --step-timeout 300] [--out eval2d_bench_table.md]
 --out writes the tables and the line under them, nothing else.  profiles/eval2d_gpu_notes.md quotes such tables inside notes written
 by hand; the tool refuses to overwrite that file."""
 import argparse
@@ -130,17 +133,77 @@ def step_kernels(shape_name, args):
                 fwd_bytes=4 * S * (x * y + PATCH[0] * PATCH[1]), back_bytes=S * (8 * x * y + 4 * CLASSES * min(x, PATCH[0]) * min(y, PATCH[1])))
 
 
-def steps():
-    for s in SHAPES:
-        yield "case|%s" % s
-    for s in SHAPES:
-        yield "kernels|%s" % s
+def step_case3(shape_name, args):
+    """One case with order=3 on the host route and on the gpu route, and with order=0 on the gpu route, alternating."""
+    import torch
+    from arco_amd import eval_surface
+    img, lab = make_case(SHAPES[shape_name])
+    net = _net()
+    routes = {"host3": dict(zoom="host", order=3), "gpu3": dict(zoom="gpu", order=3), "gpu0": dict(zoom="gpu", order=0)}
+    host_pred = eval_surface.predict_volume(img, net, PATCH, **routes["host3"])
+    same_map = bool(np.array_equal(eval_surface.predict_volume(img, net, PATCH, **routes["gpu3"]).cpu().numpy(), host_pred))
+    metrics = {k: eval_surface.test_single_volume(img, lab, net, CLASSES, PATCH, surface="gpu", **kw) for k, kw in routes.items()}
+    ts = {k: [] for k in routes}
+    for i in range(args.warmup + args.reps):
+        for k, kw in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eval_surface.test_single_volume(img, lab, net, CLASSES, PATCH, surface="gpu", **kw)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ts[k].append(time.perf_counter() - t0)
+    inp = torch.randn((img.shape[0], 1) + PATCH, device="cuda")
+    with torch.no_grad():
+        t_net = event_ms(lambda: net(inp), args.reps, args.warmup)         # the network forward of the case's slices, for scale
+    res = dict(shape=shape_name, same_map=same_map, same_metrics=metrics["host3"] == metrics["gpu3"], net=t_net,
+               differs_from_order0=bool(metrics["gpu3"] != metrics["gpu0"]), dev=torch.cuda.get_device_name(0))
+    for k in routes:
+        res[k], res[k + "_min"] = statistics.median(ts[k]) * 1e3, min(ts[k]) * 1e3
+    return res
+
+
+def step_kernels3(shape_name, args):
+    """The three launches of zoom_gpu.zoom_cubic, each alone between device events on preallocated buffers, and scipy's zoom(order=3)."""
+    import torch
+    from scipy.ndimage import zoom
+    import arco_amd._lib as L
+    from arco_amd.utils import zoom_gpu
+    S, x, y = SHAPES[shape_name]
+    img, _ = make_case(SHAPES[shape_name])
+    vol = torch.from_numpy(img).cuda()
+    coef = torch.empty((S, x, y), dtype=torch.float64, device="cuda")
+    out = torch.empty((S,) + PATCH, dtype=torch.float32, device="cuda")
+    consts = zoom_gpu.spline_constants(x, y)
+    z0, z1 = (x - 1) / (PATCH[0] - 1), (y - 1) / (PATCH[1] - 1)
+    t_cols = event_ms(lambda: L.call("arco_spline_prefilter2d", L.ptr(vol), S, x, y, *consts, 1, L.ptr(coef)), args.kernel_reps, args.warmup)
+    t_rows = event_ms(lambda: L.call("arco_spline_prefilter2d", L.ptr(vol), S, x, y, *consts, 2, L.ptr(coef)), args.kernel_reps, args.warmup)
+    t_int = event_ms(lambda: L.call("arco_zoom_cubic2d", L.ptr(coef), S, x, y, PATCH[0], PATCH[1], z0, z1, L.ptr(out)), args.kernel_reps,
+                     args.warmup)
+    t_all = event_ms(lambda: zoom_gpu.zoom_cubic(vol, PATCH), args.kernel_reps, args.warmup)
+    host = []
+    for i in range(1 + args.reps):
+        t0 = time.perf_counter()
+        for s in range(S):
+            zoom(img[s], (PATCH[0] / x, PATCH[1] / y), order=3)
+        if i:
+            host.append(time.perf_counter() - t0)
+    n = S * x * y
+    return dict(shape=shape_name, cols=t_cols, rows=t_rows, interp=t_int, all=t_all, host=statistics.median(host) * 1e3,
+                cols_bytes=(4 + 8) * n, rows_bytes=(8 + 8) * n, interp_bytes=8 * n + 4 * S * PATCH[0] * PATCH[1], lines_cols=S * y, lines_rows=S * x)
+
+
+STEPS = {"case": step_case, "kernels": step_kernels, "case3": step_case3, "kernels3": step_kernels3}
+
+
+def steps(order=0):
+    for kind in ("case", "kernels") + (("case3", "kernels3") if order == 3 else ()):
+        for s in SHAPES:
+            yield "%s|%s" % (kind, s)
 
 
 def run_step(name, args):
     kind, shape = name.split("|")
-    res = step_case(shape, args) if kind == "case" else step_kernels(shape, args)
-    print(TAG + json.dumps(res), flush=True)
+    print(TAG + json.dumps(STEPS[kind](shape, args)), flush=True)
 
 
 def main():
@@ -149,6 +212,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kernel-reps", type=int, default=50)
     ap.add_argument("--step-timeout", type=float, default=300.0, help="seconds for each step (a child process of its own)")
+    ap.add_argument("--order", type=int, default=0, choices=(0, 3), help="3: also the order-3 (cubic-spline) case and kernel rows")
     ap.add_argument("--out", default=None, help="also write the tables to this file (not profiles/eval2d_gpu_notes.md)")
     ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -156,8 +220,8 @@ def main():
         return run_step(args.step, args)
     if args.out and os.path.basename(args.out) == "eval2d_gpu_notes.md":
         raise SystemExit("eval2d_bench: profiles/eval2d_gpu_notes.md is written by hand around the tables of this tool; give --out another file")
-    case_rows, kernel_rows = [], []
-    for name in steps():
+    case_rows, kernel_rows, case3_rows, kernel3_rows = [], [], [], []
+    for name in steps(args.order):
         cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(args.reps), "--warmup", str(args.warmup),
                "--kernel-reps", str(args.kernel_reps)]
         try:
@@ -170,7 +234,15 @@ def main():
             print(p.stdout)
             raise SystemExit("eval2d_bench: step %r failed with exit status %d; nothing more is started" % (name, p.returncode))
         r = found[0]
-        if name.startswith("case"):
+        if name.startswith("case3"):
+            case3_rows.append(r)
+            print("%-11s order 3 per case: zoom=host %8.2f ms, zoom=gpu %8.2f ms; order 0 zoom=gpu %8.2f ms; net forward %.2f ms" %
+                  (r["shape"], r["host3"], r["gpu3"], r["gpu0"], r["net"]), flush=True)
+        elif name.startswith("kernels3"):
+            kernel3_rows.append(r)
+            print("%-11s prefilter axis 0 %.4f ms, axis 1 %.4f ms, interpolation %.4f ms, zoom_cubic %.4f ms, scipy %.1f ms" %
+                  (r["shape"], r["cols"], r["rows"], r["interp"], r["all"], r["host"]), flush=True)
+        elif name.startswith("case"):
             case_rows.append(r)
             print("%-11s test_single_volume per case: zoom=host %8.2f ms, zoom=gpu %8.2f ms" % (r["shape"], r["host"], r["gpu"]), flush=True)
         else:
@@ -194,6 +266,29 @@ def main():
             (cpu_model(), case_rows[0]["dev"], args.reps, args.warmup,
              "; ".join("%s %.2f / %.2f ms" % (r["shape"], r["host_min"], r["gpu_min"]) for r in case_rows), args.kernel_reps, args.warmup,
              args.reps, PATCH[0], PATCH[1], CLASSES, ", ".join("%s %d" % (r["shape"], r["classes_predicted"]) for r in case_rows)))
+    if args.order == 3:
+        lines = ["", "| Volume | order=3, zoom=\"host\" | order=3, zoom=\"gpu\" | order=0, zoom=\"gpu\" | host3 / gpu3 | net forward of the case |",
+                 "|---|---|---|---|---|---|"]
+        for r in case3_rows:
+            lines.append("| %s | %.2f ms | %.2f ms | %.2f ms | %.2fx | %.2f ms |" % (r["shape"], r["host3"], r["gpu3"], r["gpu0"],
+                                                                                r["host3"] / r["gpu3"], r["net"]))
+        lines += ["", "| Volume | prefilter axis 0 (lines) | prefilter axis 1 (lines) | interpolation | zoom_cubic, all three | scipy zoom(order=3), same slices |",
+                  "|---|---|---|---|---|---|"]
+        for r in kernel3_rows:
+            lines.append("| %s | %.4f ms, floor %.2f MB (%.0f GB/s), %d | %.4f ms, floor %.2f MB (%.0f GB/s), %d | %.4f ms, floor %.2f MB (%.0f GB/s) | "
+                         "%.4f ms | %.1f ms |" %
+                         (r["shape"], r["cols"], r["cols_bytes"] / 1e6, r["cols_bytes"] / r["cols"] / 1e6, r["lines_cols"], r["rows"],
+                          r["rows_bytes"] / 1e6, r["rows_bytes"] / r["rows"] / 1e6, r["lines_rows"], r["interp"], r["interp_bytes"] / 1e6,
+                          r["interp_bytes"] / r["interp"] / 1e6, r["all"], r["host"]))
+        table += "\n" + "\n".join(lines)
+        note += ("\n\nOrder 3: the three routes alternate in one process (fastest runs: %s).  zoom=\"gpu\", order=3 gave the label map of "
+                 "zoom=\"host\", order=3: %s; the same metrics: %s; metrics other than order 0's: %s.  Byte floor of a kernel: every array it reads "
+                 "or writes counted once (float32 in and float64 out for axis 0; float64 in and out for axis 1; float64 in and float32 out "
+                 "for the interpolation); the kernels are timed on preallocated buffers, zoom_cubic with its two allocations." %
+                 ("; ".join("%s %.2f / %.2f / %.2f ms" % (r["shape"], r["host3_min"], r["gpu3_min"], r["gpu0_min"]) for r in case3_rows),
+                  ", ".join("%s %s" % (r["shape"], "yes" if r["same_map"] else "NO") for r in case3_rows),
+                  ", ".join("%s %s" % (r["shape"], "yes" if r["same_metrics"] else "NO") for r in case3_rows),
+                  ", ".join("%s %s" % (r["shape"], "yes" if r["differs_from_order0"] else "no") for r in case3_rows)))
     print(table + "\n\n" + note)
     if args.out:
         with open(args.out, "w") as f:
