@@ -50,6 +50,7 @@ _SIGS = {
     "arco_cc_value_largest": [_P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P],
     "arco_zoom_nearest2d": [_P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _I, _P, _P],
     "arco_argmax_zoom_back2d": [_P, _L, _I, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P],
+    "arco_argmax_zoom_back2d_h": [_P, _L, _I, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P],
     "arco_spline_prefilter2d": [_P, _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P, _P],
     "arco_zoom_cubic2d": [_P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P],
     "arco_mix_unsup": [_P, _I, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P],
@@ -92,6 +93,7 @@ _SIGS = {
     "arco_conv3x3_image_fwd_h": [_P, _L, _I, _P, _I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _P],
     "arco_conv3x3_image_wgrad_h": [_P, _L, _I, _P, _L, _I, _I, _I, _I, _P, _P, _I, _P],
     "arco_maxpool2_fwd_h": [_P, _L, _I, _I, _I, _I, _P, _L, _P],
+    "arco_bn_act_pool_fwd_h": [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _F, _P, _L, _P, _L, _I, _P],
     "arco_maxpool2_bwd_h": [_P, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P],
     "arco_maxpool2_bwd_add_h": [_P, _L, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P],
     "arco_bilinear_fwd_h": [_P, _L, _I, _I, _I, _I, _I, _I, _P, _L, _P],

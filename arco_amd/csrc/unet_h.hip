@@ -181,6 +181,59 @@ __global__ __launch_bounds__(256) void hmaxpool2_fwd_kernel(const _Float16* __re
     st8h(Y + (((n * Ho) + yo) * Wo + xo) * ldy + c, o);
   }
 }
+// BatchNorm apply + LeakyReLU of an encoder block's last stage AND the 2x2 max-pool of the result in one pass over the f16
+// pre-activation (bn_act_pool_fwd_kernel's form on f16 storage; the f16 inference route, ops.eval_half): a thread owns a 2x2 pixel
+// window x V channels (V = 8: 16-byte accesses; V = 4: 8-byte ones, for rows that are not whole 16-byte pieces) - four Z loads,
+// four A stores, one pooled store.  Per element the fp32 expression of bn_act_fwd_kernel<_Float16>, rounded once to f16; the
+// pooled value is the maximum of the four ROUNDED values in hmaxpool2_fwd_kernel's order - both outputs equal, bit for bit,
+// arco_bn_act_fwd_h followed by arco_maxpool2_fwd_h.  A may be the leading channels of a wider buffer (lda > C: concat room).
+template <int V>
+__global__ __launch_bounds__(256) void hbn_act_pool_fwd_kernel(const _Float16* __restrict__ Z, long ldz, int NB, int H, int W, int C,
+                                                              const float* __restrict__ mean, const float* __restrict__ istd,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              float slope, _Float16* __restrict__ Aout, long lda,
+                                                              _Float16* __restrict__ Pout, long ldp, int img_per_group) {
+  typedef float fv __attribute__((ext_vector_type(V)));
+  typedef _Float16 hv __attribute__((ext_vector_type(V)));
+  const int qv = C / V, Ho = H / 2, Wo = W / 2;
+  const long tot = (long)NB * Ho * Wo * qv;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tot; i += (long)gridDim.x * 256) {
+    const int c = (int)(i % qv) * V; long r = i / qv;
+    const int xo = r % Wo; r /= Wo; const int yo = r % Ho; const long n = r / Ho;
+    const long g = n / img_per_group;
+    fv mu, is, ga, be;
+#pragma unroll
+    for (int e = 0; e < V; e += 4) {
+      const f32x4 m4 = *reinterpret_cast<const f32x4*>(mean + g * C + c + e), i4 = *reinterpret_cast<const f32x4*>(istd + g * C + c + e);
+      const f32x4 g4 = *reinterpret_cast<const f32x4*>(gamma + c + e), b4 = *reinterpret_cast<const f32x4*>(beta + c + e);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { mu[e + k] = m4[k]; is[e + k] = i4[k]; ga[e + k] = g4[k]; be[e + k] = b4[k]; }
+    }
+    const long row = ((n * H) + 2 * yo) * W + 2 * xo;
+    const long rows[4] = {row, row + 1, row + W, row + W + 1};
+    fv z[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) z[u] = __builtin_convertvector(*reinterpret_cast<const hv*>(Z + rows[u] * ldz + c), fv);
+    fv o[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      fv a;
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        float y = (z[u][e] - mu[e]) * is[e] * ga[e] + be[e];
+        y = y >= 0.f ? y : y * slope;
+        a[e] = y;
+      }
+      const hv ah = __builtin_convertvector(a, hv);
+      *reinterpret_cast<hv*>(Aout + rows[u] * lda + c) = ah;
+      o[u] = __builtin_convertvector(ah, fv);                      // the pooling reads what was stored
+    }
+    fv m;
+#pragma unroll
+    for (int e = 0; e < V; ++e) m[e] = fmaxf(fmaxf(o[0][e], o[1][e]), fmaxf(o[2][e], o[3][e]));
+    *reinterpret_cast<hv*>(Pout + (((n * Ho) + yo) * Wo + xo) * ldp + c) = __builtin_convertvector(m, hv);
+  }
+}
 // gradient goes to the first maximum in window scan order (as maxpool2_bwd_kernel / torch's saved argmax)
 __global__ __launch_bounds__(256) void hmaxpool2_bwd_kernel(const _Float16* __restrict__ X, long ldx, int NB, int H, int W, int C,
                                                            const _Float16* __restrict__ dY, long ldy, _Float16* __restrict__ dX,
@@ -321,6 +374,27 @@ int arco_maxpool2_fwd_h(const void* X, long ldx, int NB, int H, int W, int C, vo
   ARCO_CHECK_ARG(C > 0 && (C & 7) == 0 && (H & 1) == 0 && (W & 1) == 0 && NB > 0 && arco_h8_ok({X, Y}, {ldx, ldy}));
   hipLaunchKernelGGL(hmaxpool2_fwd_kernel, dim3(uh_grid((long)NB * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<const _Float16*>(X), ldx, NB, H, W, C, reinterpret_cast<_Float16*>(Y), ldy);
+  return arco_launch_status();
+}
+// A (f16) [pix][0..C) = lrelu(BN(Z (f16))) and P (f16) = maxpool2(A) in one pass; mean / istd [groups][C], gamma / beta [C], fp32.
+// 16-byte lanes where every pointer and row stride allows them, else 8-byte lanes (C and the strides multiples of 4).
+int arco_bn_act_pool_fwd_h(const void* Z, long ldz, int NB, int H, int W, int C, const float* mean, const float* istd,
+                           const float* gamma, const float* beta, float slope, void* A, long lda, void* P, long ldp, int groups,
+                           void* stream) {
+  if (groups < 1) groups = 1;
+  ARCO_CHECK_ARG(Z && mean && istd && gamma && beta && A && P && NB > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && (H & 1) == 0 &&
+                 (W & 1) == 0 && NB % groups == 0 && ldz >= C && lda >= C && ldp >= C && ((ldz | lda | ldp) & 3) == 0);
+  for (const void* p : {Z, (const void*)A, (const void*)P}) ARCO_CHECK_ARG((reinterpret_cast<uintptr_t>(p) & 7) == 0);
+  for (const void* p : {(const void*)mean, (const void*)istd, (const void*)gamma, (const void*)beta})
+    ARCO_CHECK_ARG((reinterpret_cast<uintptr_t>(p) & 15) == 0);
+  const _Float16* z = reinterpret_cast<const _Float16*>(Z);
+  _Float16* a = reinterpret_cast<_Float16*>(A); _Float16* p = reinterpret_cast<_Float16*>(P);
+  if ((C & 7) == 0 && arco_h8_ok({Z, A, P}, {ldz, lda, ldp}))
+    hipLaunchKernelGGL(hbn_act_pool_fwd_kernel<8>, dim3(uh_grid((long)NB * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, as_stream(stream),
+                       z, ldz, NB, H, W, C, mean, istd, gamma, beta, slope, a, lda, p, ldp, NB / groups);
+  else
+    hipLaunchKernelGGL(hbn_act_pool_fwd_kernel<4>, dim3(uh_grid((long)NB * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0, as_stream(stream),
+                       z, ldz, NB, H, W, C, mean, istd, gamma, beta, slope, a, lda, p, ldp, NB / groups);
   return arco_launch_status();
 }
 int arco_maxpool2_bwd_h(const void* X, long ldx, int NB, int H, int W, int C, const void* dY, long ldy, void* dX, long ldo,

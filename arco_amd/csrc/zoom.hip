@@ -72,12 +72,32 @@ __global__ __launch_bounds__(256) void zoom_nearest_kernel(const T* __restrict__
 // softmax_rows_kernel's `amax` of one logits row: the same expressions in the same order, compiled as glue.hip compiles them (the
 // file's contraction switch is undone for this body) - mx by fmaxf, expf(v - mx), the sum in class order, p = e / s and the first
 // strict maximum of p.  Not the arg-max of the logits: logits a fraction of an ulp of 1 apart give equal fp32 probabilities.
-__device__ __forceinline__ long row_class(const float* __restrict__ x, int C) {
+// f16 rows (T = _Float16; arco_argmax_zoom_back2d_h) are widened to fp32 first - exact, so the class is the one the fp32 kernel gives
+// for the fp32 cast of the row -, four classes per 8-byte load where `vec` says that every row allows it, one by one otherwise and at
+// the ragged end of a row.
+template <typename T>
+__device__ __forceinline__ long row_class(const T* __restrict__ x, int C, bool vec) {
 #pragma clang fp contract(fast)
   float v[ZOOM_MAXC];
   float mx = -INFINITY;
+  if constexpr (sizeof(T) == 2) {
 #pragma unroll
-  for (int c = 0; c < ZOOM_MAXC; ++c) if (c < C) { v[c] = x[c]; mx = fmaxf(mx, v[c]); }
+    for (int c = 0; c < ZOOM_MAXC; c += 4) {
+      if (vec && c + 4 <= C) {
+        const f32x4 w = ld4f(x + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[c + e] = w[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) if (c + e < C) v[c + e] = (float)x[c + e];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < ZOOM_MAXC; ++c) if (c < C) mx = fmaxf(mx, v[c]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < ZOOM_MAXC; ++c) if (c < C) { v[c] = x[c]; mx = fmaxf(mx, v[c]); }
+  }
   float s = 0.f;
 #pragma unroll
   for (int c = 0; c < ZOOM_MAXC; ++c) if (c < C) { v[c] = expf(v[c] - mx); s += v[c]; }
@@ -91,8 +111,10 @@ __device__ __forceinline__ long row_class(const float* __restrict__ x, int C) {
 }
 
 // one thread: two consecutive labels of output row (s, i); runs = ceil(N1 / 2) per row
-__global__ __launch_bounds__(256) void argmax_zoom_back_kernel(const float* __restrict__ X, long ld, int C, int P0, int P1, int N0, int N1,
+template <typename T>
+__global__ __launch_bounds__(256) void argmax_zoom_back_kernel(const T* __restrict__ X, long ld, int C, int P0, int P1, int N0, int N1,
                                                                int runs, long total, double z0, double z1, long* __restrict__ out) {
+  const bool vec = sizeof(T) == 2 && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 7) == 0;     // every f16 row starts 8-byte aligned
   const long q = (long)blockIdx.x * 256 + threadIdx.x;
   if (q >= total) return;
   const long row = q / runs;
@@ -101,11 +123,11 @@ __global__ __launch_bounds__(256) void argmax_zoom_back_kernel(const float* __re
   long v[2] = {0, 0};
   int su;
   if (zoom_index(i, z0, P0, su)) {
-    const float* line = X + (s * P0 + su) * P1 * ld;
+    const T* line = X + (s * P0 + su) * P1 * ld;
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       int sv;
-      if (j0 + e < N1 && zoom_index(j0 + e, z1, P1, sv)) v[e] = row_class(line + sv * ld, C);
+      if (j0 + e < N1 && zoom_index(j0 + e, z1, P1, sv)) v[e] = row_class(line + sv * ld, C, vec);
     }
   }
   store_run<long, 2>(out + row * N1 + j0, v, min(2, N1 - j0));
@@ -366,17 +388,30 @@ int arco_zoom_nearest2d(const void* src, int S, int n0, int n1, int N0, int N1, 
   return arco_launch_status();
 }
 
-int arco_argmax_zoom_back2d(const float* X, long ld, int C, int n, int P0, int P1, int N0, int N1, double z0, double z1, int64_t* out,
-                            void* stream) {
+extern "C++" {
+template <typename T>
+static int argmax_zoom_back_impl(const T* X, long ld, int C, int n, int P0, int P1, int N0, int N1, double z0, double z1, int64_t* out,
+                                 void* stream) {
   ARCO_CHECK_ARG(X && out && C >= 1 && C <= ZOOM_MAXC && ld >= C && n >= 1 && P0 >= 1 && P1 >= 1 && N0 >= 2 && N1 >= 2);
   ARCO_CHECK_ARG(zoom_step_ok(z0) && zoom_step_ok(z1));
   const int runs = (N1 + 1) / 2;
   const long total = (long)n * N0 * runs;
   unsigned blocks;
   ARCO_CHECK_ARG(zoom_grid(total, blocks));
-  hipLaunchKernelGGL(argmax_zoom_back_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), X, ld, C, P0, P1, N0, N1, runs, total, z0, z1,
-                     reinterpret_cast<long*>(out));
+  hipLaunchKernelGGL(argmax_zoom_back_kernel<T>, dim3(blocks), dim3(256), 0, as_stream(stream), X, ld, C, P0, P1, N0, N1, runs, total, z0,
+                     z1, reinterpret_cast<long*>(out));
   return arco_launch_status();
+}
+}  // extern "C++"
+int arco_argmax_zoom_back2d(const float* X, long ld, int C, int n, int P0, int P1, int N0, int N1, double z0, double z1, int64_t* out,
+                            void* stream) {
+  return argmax_zoom_back_impl<float>(X, ld, C, n, P0, P1, N0, N1, z0, z1, out, stream);
+}
+// ... reading f16 logits rows (2-byte aligned at least): the class arco_argmax_zoom_back2d gives for the fp32 cast of the same rows
+int arco_argmax_zoom_back2d_h(const void* X, long ld, int C, int n, int P0, int P1, int N0, int N1, double z0, double z1, int64_t* out,
+                              void* stream) {
+  ARCO_CHECK_ARG((reinterpret_cast<uintptr_t>(X) & 1) == 0);
+  return argmax_zoom_back_impl<_Float16>(reinterpret_cast<const _Float16*>(X), ld, C, n, P0, P1, N0, N1, z0, z1, out, stream);
 }
 
 int arco_spline_prefilter2d(const float* src, int S, int n0, int n1, double z, double gain, double zn0, double zn1, int axes, double* out,

@@ -28,12 +28,21 @@ What `nms` keeps: test_all_case takes `nms_mode="foreground"` (default: getLarge
 cc_gpu.largest_per_class); the keyword is read only when `nms` is set, any other value is a ValueError before any GPU work.
 test_single_volume takes `nms=0, cc="host"`: nms=1 keeps each class's largest component of the [S, X, Y] prediction (csrc/cc.hip by value on
 cc="gpu", which needs surface="gpu") before the overlap counts and the surface metrics.
+predict_volume, test_single_volume, predict_case and test_all_case take `act_dtype="f32"` (default: every path exactly as without the
+keyword) or "f16": the forwards of that call run inside `ops.eval_half()` - the U-Net / the V-Net (batchnorm) keep their activations as
+f16 -, everything before and after them is unchanged.  With zoom="gpu" predict_volume takes the logits as the f16 tensor the last
+convolution wrote (`eval_half(logits="stored")`) into arco_argmax_zoom_back2d_h; on zoom="host" and in predict_case the logits leave as
+fp32 and go through the same softmax / window kernels as before.  The switches of `ops` are put back when the call returns or raises.
+Any other value is a ValueError before any GPU work.
 Inference, the sliding window, the overlap counts and the empty-set conventions are those modules' own."""
+import contextlib
+
 import numpy as np
 import torch
 
 from . import _lib as _L
 from . import glue as _glue
+from . import ops as _ops
 from . import test_2D as _t2d
 from . import test_util as _t3d
 from .utils import cc_gpu as _cc_gpu
@@ -74,6 +83,21 @@ def _check_nms_mode(nms_mode):
     if nms_mode not in NMS_MODES:
         raise ValueError(f"nms_mode must be one of {NMS_MODES}, got {nms_mode!r}")
     return nms_mode
+
+
+ACT_DTYPES = ("f32", "f16")
+
+
+def check_act_dtype(act_dtype):
+    """The `act_dtype=` keyword of the inference entry points: "f32" (default) or "f16" (the forwards inside `ops.eval_half()`)."""
+    if act_dtype not in ACT_DTYPES:
+        raise ValueError(f"act_dtype must be one of {ACT_DTYPES}, got {act_dtype!r}")
+    return act_dtype
+
+
+def _act_scope(act_dtype, logits="f32"):
+    """The scope the forwards of a call run in: `ops.eval_half` for "f16", nothing for "f32"."""
+    return _ops.eval_half(logits=logits) if act_dtype == "f16" else contextlib.nullcontext()
 
 
 def _shape(x):
@@ -118,24 +142,28 @@ def calculate_metric_percase_2d(pred, gt, surface="host", voxelspacing=None, con
 
 
 @torch.no_grad()
-def _predict_volume_host(image, net, patch_size, batch=32, device="cuda:0", order=0):
-    """The host route's label map, an int64 numpy array.  order=0 is a plain call of test_2D.predict_volume.  order=3 restates its loop
+def _predict_volume_host(image, net, patch_size, batch=32, device="cuda:0", order=0, act_dtype="f32"):
+    """The host route's label map, an int64 numpy array.  order=0, act_dtype="f32" is a plain call of test_2D.predict_volume.  Otherwise
+    its loop is restated here, order 0 with the two zoom calls as that module makes them and the forward inside `ops.eval_half()` for
+    act_dtype="f16" (the logits leave as fp32).  order=3 restates the loop
     (that module stays as it is) with the reference's test.py:116-135 in place of the two zoom calls: a slice goes to the patch by
     scipy's zoom(order=3) only when its size differs from the patch - a slice of patch size is passed as it is, a cubic zoom by 1.0 is
     not the identity in bits - and the arg-max map comes back by order 0 under the same condition."""
-    if order == 0:
+    if order == 0 and act_dtype == "f32":
         return _t2d.predict_volume(image, net, patch_size, batch=batch, device=device)
     from scipy.ndimage import zoom
     image = np.asarray(image)
     S, x, y = image.shape
-    as_is = (x, y) == (patch_size[0], patch_size[1])
-    zoomed = image if as_is else np.stack([zoom(image[i], (patch_size[0] / x, patch_size[1] / y), order=3) for i in range(S)])
+    as_is = order == 3 and (x, y) == (patch_size[0], patch_size[1])          # (order 0 zooms every slice, as test_2D does)
+    zoomed = image if as_is else np.stack([zoom(image[i], (patch_size[0] / x, patch_size[1] / y), order=order) for i in range(S)])
     prediction = np.zeros((S, x, y), dtype=np.int64)
     was_training = net.training
     net.eval()
     for s0 in range(0, S, batch):
         inp = torch.from_numpy(np.ascontiguousarray(zoomed[s0:s0 + batch])).unsqueeze(1).float().to(device)
-        out = _glue.softmax_max(net(inp)[0])[1].cpu().numpy()
+        with _act_scope(act_dtype):
+            logits = net(inp)[0]
+        out = _glue.softmax_max(logits)[1].cpu().numpy()
         for i in range(out.shape[0]):
             prediction[s0 + i] = out[i] if as_is else zoom(out[i], (x / patch_size[0], y / patch_size[1]), order=0)
     if was_training:
@@ -144,7 +172,7 @@ def _predict_volume_host(image, net, patch_size, batch=32, device="cuda:0", orde
 
 
 @torch.no_grad()
-def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0", zoom="host", order=0):
+def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0", zoom="host", order=0, act_dtype="f32"):
     """Label map of a [S, X, Y] volume.  zoom="host": test_2D.predict_volume, an int64 numpy array.  zoom="gpu": the same label map as an
     int64 tensor ON THE DEVICE - the volume is uploaded once as float32 (nearest sampling and zero fill commute with the cast),
     zoom_gpu.zoom_nearest takes every slice to the patch, the eval-mode net runs in the same batches, and zoom_gpu.argmax_zoom_back
@@ -152,11 +180,14 @@ def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0",
     come back to (X, Y) (the host route fails on its assignment there).
     order=3: the slices go to the patch by the cubic-spline zoom where their size differs from the patch (test.py:123-124) and as they
     are where it does not - scipy's zoom(order=3) on the host, zoom_gpu.zoom_cubic on the device, where the volume must be
-    float32 -; the way back is unchanged (at patch size argmax_zoom_back samples every pixel: the arg-max map itself)."""
+    float32 -; the way back is unchanged (at patch size argmax_zoom_back samples every pixel: the arg-max map itself).
+    act_dtype="f16": the forwards run inside `ops.eval_half()`; on zoom="gpu" the logits stay the f16 tensor the last convolution
+    wrote and argmax_zoom_back reads them as stored (arco_argmax_zoom_back2d_h) - no fp32 logits exist."""
     _zoom_gpu.check_zoom(zoom)
     _zoom_gpu.check_order(order)
+    check_act_dtype(act_dtype)
     if zoom == "host":
-        return _predict_volume_host(image, net, patch_size, batch=batch, device=device, order=order)
+        return _predict_volume_host(image, net, patch_size, batch=batch, device=device, order=order, act_dtype=act_dtype)
     image = np.asarray(image)
     if order == 3 and image.dtype != np.float32:
         raise ValueError("zoom=\"gpu\", order=3 takes a float32 volume (the cast does not commute with the spline): cast it with "
@@ -177,7 +208,8 @@ def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0",
     was_training = net.training
     net.eval()
     for s0 in range(0, S, batch):
-        logits = net(zoomed[s0:s0 + batch].unsqueeze(1))[0]
+        with _act_scope(act_dtype, logits="stored"):
+            logits = net(zoomed[s0:s0 + batch].unsqueeze(1))[0]
         prediction[s0:s0 + batch] = _zoom_gpu.argmax_zoom_back(logits, (x, y))
     if was_training:
         net.train()
@@ -186,7 +218,7 @@ def predict_volume(image, net, patch_size=(256, 256), batch=32, device="cuda:0",
 
 @torch.no_grad()
 def test_single_volume(image, label, net, classes, patch_size=(256, 256), device="cuda:0", surface="host", zoom="host",
-                       voxelspacing=None, connectivity=1, nms=0, cc="host", order=0):
+                       voxelspacing=None, connectivity=1, nms=0, cc="host", order=0, act_dtype="f32"):
     """test_2D.test_single_volume; with surface="gpu" the surface metrics of all classes come from one call on the label volumes that
     are on the device for the overlap counts already.  zoom="gpu" (with surface="gpu" only) is the device-resident case: the label map
     of predict_volume(zoom="gpu") goes to the overlap counts and the surface kernels as the device tensor it is.  Every class is scored on
@@ -194,20 +226,22 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), device
     nms=1 keeps, before anything is counted or measured, only the largest component of every class of the [S, X, Y] prediction (the 3-D
     object it is, full connectivity): cc="host" (default) through cc_host.keep_largest_per_class on the host map, cc="gpu" (with
     surface="gpu" only) through cc_gpu.largest_per_class - with zoom="gpu" the label map then never leaves the device.
-    order=3 is predict_volume's: the cubic-spline zoom of the slices to the patch on either route, everything after it unchanged."""
+    order=3 is predict_volume's: the cubic-spline zoom of the slices to the patch on either route, everything after it unchanged.
+    act_dtype="f16" is predict_volume's too: the forwards inside `ops.eval_half()`, everything around them unchanged."""
     _surface_gpu.check_route(surface)
     _zoom_gpu.check_order(order)
+    check_act_dtype(act_dtype)
     if _zoom_gpu.check_zoom(zoom) == "gpu" and surface != "gpu":
         raise ValueError('zoom="gpu" is the device-resident head of surface="gpu"; got surface=%r' % (surface,))
     if _cc_gpu.check_cc(cc) == "gpu" and surface != "gpu":
         raise ValueError('cc="gpu" is the device-resident tail of surface="gpu"; got surface=%r' % (surface,))
     unit = _unit(voxelspacing, connectivity)
-    if surface == "host" and unit and not nms and order == 0:
+    if surface == "host" and unit and not nms and order == 0 and act_dtype == "f32":
         return _t2d.test_single_volume(image, label, net, classes, patch_size, device=device)
     if not unit:
         _surface_gpu.check_spaced_args(voxelspacing, connectivity, 3)
     if surface == "host":
-        prediction = _predict_volume_host(image, net, patch_size, device=device, order=order)
+        prediction = _predict_volume_host(image, net, patch_size, device=device, order=order, act_dtype=act_dtype)
         if nms:
             prediction = _cc_host.keep_largest_per_class(prediction)
         cnt = _t2d.overlap_counts(torch.from_numpy(prediction).to(device), torch.from_numpy(np.asarray(label, dtype=np.int64)).to(device),
@@ -215,11 +249,11 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), device
         return _metric_list(cnt, classes, lambda c: (_binary.hd95(prediction == c, label == c, voxelspacing, connectivity),
                                                      _binary.asd(prediction == c, label == c, voxelspacing, connectivity)))
     if zoom == "gpu":
-        pred_d = predict_volume(image, net, patch_size, device=device, zoom="gpu", order=order)
+        pred_d = predict_volume(image, net, patch_size, device=device, zoom="gpu", order=order, act_dtype=act_dtype)
         if nms and cc == "host":
             pred_d = torch.from_numpy(_cc_host.keep_largest_per_class(pred_d.cpu().numpy())).to(device)
     else:
-        prediction = _predict_volume_host(image, net, patch_size, device=device, order=order)
+        prediction = _predict_volume_host(image, net, patch_size, device=device, order=order, act_dtype=act_dtype)
         if nms and cc == "host":
             prediction = _cc_host.keep_largest_per_class(prediction)
         pred_d = torch.from_numpy(prediction).to(device)
@@ -245,11 +279,14 @@ def calculate_metric_percase_3d(pred, gt, surface="host", voxelspacing=None, con
 
 
 @torch.no_grad()
-def predict_case(net, image, stride_xy, stride_z, patch_size, num_classes, batch=4, device="cuda:0"):
+def predict_case(net, image, stride_xy, stride_z, patch_size, num_classes, batch=4, device="cuda:0", act_dtype="f32"):
     """The label map of test_util.test_single_case as an int64 tensor [w, h, d] that stays ON THE DEVICE: neither it nor the score map
     is copied to the host.  The window loop is test_single_case's, restated (that module stays as it is): the same padding, the same
     windows in the same order, the same arco_window_accumulate / arco_score_finalize launches and the same crop;
-    tests/test_eval_cc_gpu.py holds the two to each other (array_equal, ragged and padded volumes)."""
+    tests/test_eval_cc_gpu.py holds the two to each other (array_equal, ragged and padded volumes).
+    act_dtype="f16": every forward runs inside `ops.eval_half()` (the V-Net's f16 route); the logits leave as fp32 and the softmax and
+    the window accumulation are the same launches."""
+    check_act_dtype(act_dtype)
     image = np.asarray(image)
     w, h, d = image.shape
     pads = []
@@ -272,7 +309,8 @@ def predict_case(net, image, stride_xy, stride_z, patch_size, num_classes, batch
     for s0 in range(0, len(starts), batch):
         grp = starts[s0:s0 + batch]
         patches = torch.stack([vol[xs:xs + px, ys:ys + py, zs:zs + pz] for xs, ys, zs in grp]).unsqueeze(1)
-        y1 = net(patches)
+        with _act_scope(act_dtype):
+            y1 = net(patches)
         if isinstance(y1, (tuple, list)):
             y1 = y1[0]
         assert int(y1.shape[1]) == C, (y1.shape, C)
@@ -304,7 +342,7 @@ def _metric_percase_3d_device(pred, gt, voxelspacing=None, connectivity=1):
 
 def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, preproc_fn=None,
                   metric_detail=0, nms=0, device="cuda:0", surface="host", cc="host", voxelspacing=None, connectivity=1,
-                  nms_mode="foreground"):
+                  nms_mode="foreground", act_dtype="f32"):
     """test_util.test_all_case: the mean (dice, jc, hd95, asd) over `cases` (an all-background prediction scores (0, 0, 0, 0)).
     cc="host" (default) takes the largest component of `nms` from test_util.getLargestCC on the host; cc="gpu" (with surface="gpu"
     only) is the device-resident tail: the label map of predict_case stays a device tensor, goes through cc_gpu.largest_cc with `nms`,
@@ -313,13 +351,16 @@ def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_x
     reference calls, joins only voxels of the same value): equal for the two-class case `nms` is used on, not for more classes.
     nms_mode (read only when `nms` is set) chooses what `nms` keeps: "foreground" (default) is that getLargestCC / largest_cc; "value" is
     the reference's own meaning, the largest component of equal values (cc_host.getLargestCC_by_value / cc_gpu.largest_cc_by_value);
-    "per_class" keeps the largest component of every class (cc_host.keep_largest_per_class / cc_gpu.largest_per_class)."""
+    "per_class" keeps the largest component of every class (cc_host.keep_largest_per_class / cc_gpu.largest_per_class).
+    act_dtype="f16": the forwards of every case run inside `ops.eval_half()` - predict_case's on cc="gpu", test_util.test_single_case's
+    (that module stays as it is; the scope is entered around the call) otherwise."""
     _surface_gpu.check_route(surface)
+    check_act_dtype(act_dtype)
     if _cc_gpu.check_cc(cc) == "gpu" and surface != "gpu":
         raise ValueError('cc="gpu" is the device-resident tail of surface="gpu"; got surface=%r' % (surface,))
     mode = _check_nms_mode(nms_mode) if nms else "foreground"
     unit = _unit(voxelspacing, connectivity)
-    if surface == "host" and unit and mode == "foreground":
+    if surface == "host" and unit and mode == "foreground" and act_dtype == "f32":
         return _t3d.test_all_case(model, cases, num_classes, patch_size=patch_size, stride_xy=stride_xy, stride_z=stride_z,
                                   preproc_fn=preproc_fn, metric_detail=metric_detail, nms=nms, device=device)
     if not unit:
@@ -329,13 +370,14 @@ def test_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_x
         if preproc_fn is not None:
             image = preproc_fn(image)
         if cc == "gpu":
-            prediction = predict_case(model, image, stride_xy, stride_z, patch_size, num_classes, device=device)
+            prediction = predict_case(model, image, stride_xy, stride_z, patch_size, num_classes, device=device, act_dtype=act_dtype)
             if nms:
                 prediction = _NMS[mode][1](prediction, num_classes)
             single = _metric_percase_3d_device(prediction, torch.from_numpy(np.asarray(label) != 0).to(prediction.device),
                                                voxelspacing, connectivity)
         else:
-            prediction, _ = _t3d.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, device=device)
+            with _act_scope(act_dtype):
+                prediction, _ = _t3d.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, device=device)
             if nms:
                 prediction = _NMS[mode][0](prediction)
             single = ((0, 0, 0, 0) if np.sum(prediction) == 0 else

@@ -12,8 +12,12 @@ BN finalize -> one fused BN-apply + LeakyReLU + dropout pass.
 With ops.ACT_HALF (train_arco_2d --act_dtype f16) a TRAINING-mode forward keeps every activation and activation gradient of the
 network as f16 (csrc/conv_h.hip, csrc/unet_h.hip, the *_h entry points): the first layer reads the fp32 image and writes f16, the
 logits and the feature maps leave as fp32 (ops.from_half, whose backward applies the loss scale).  The two stages of a ConvBlock
-and the pooling run as separate passes there (no consumer-side activation / pooled apply kernel in f16).  Evaluation-mode
-forwards stay on the fp32 route whatever ops.ACT_HALF says.
+and the pooling run as separate passes there (no consumer-side activation in f16; the pooled apply kernel in f16 serves inference).
+Evaluation-mode forwards stay on the fp32 route whatever ops.ACT_HALF says.  F16 INFERENCE is opt-in and scoped: inside
+`with ops.eval_half():` an evaluation-mode forward opens the f16 region at in_conv's first layer, runs every stage on f16 tensors
+(the encoder blocks write their activation and its 2x2 max-pool in one pass, arco_bn_act_pool_fwd_h; dropout stays inactive) and
+hands the logits and the feature maps out as fp32 - or, with `ops.eval_half(logits="stored")`, the logits as the f16 tensor the
+last convolution wrote.  arco_amd.eval_surface reaches it with act_dtype="f16".
 """
 import torch
 import torch.nn as nn
@@ -32,7 +36,9 @@ def _stage(x, conv, bn, act, drop_p, training, drop_mode=1, cat_room=0, pool=Fal
                             slope=slope, p=drop_p, drop_mode=drop_mode, momentum=bn.momentum, eps=bn.eps,
                             num_batches_tracked=bn.num_batches_tracked, cat_room=cat_room, pool=pool)
         return y
-    assert not pool
+    if pool:                          # the f16 inference route (ops.eval_half): the pooled apply pass, with concat room
+        return ops.conv_bn_act_eval(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                    slope=slope, eps=bn.eps, cat_room=cat_room, pool=True)
     return ops.conv_bn_act_eval(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                                 slope=slope, eps=bn.eps)
 
@@ -55,7 +61,8 @@ class ConvBlock(nn.Module):
     cat_room = 0      # Encoder sets it on the blocks whose output is a skip connection (see ops.upcat)
 
     def forward(self, x, pool=False):
-        """pool=True (train mode): (block output, its 2x2 max-pool) - the pooling rides on the last BN / activation pass."""
+        """pool=True (train mode, and the f16 inference route): (block output, its 2x2 max-pool) - the pooling rides on the last
+        BN / activation pass."""
         s = self.conv_conv
         if self.training:
             # both stages as one node: the first stage's activation is formed in the second convolution's loader (ops.ConvBlockFn)
@@ -142,10 +149,18 @@ class Encoder(nn.Module):
 
     def forward(self, x):
         x = ops.to_channels_last(x.to(torch.float32))
-        with ops.open_half(self.training and ops.ACT_HALF):      # f16 activation storage: in_conv's first layer opens the region
+        # f16 activation storage: in_conv's first layer opens the region - training under ACT_HALF, evaluation inside ops.eval_half()
+        with ops.open_half(ops.ACT_HALF if self.training else ops.EVAL_HALF):
             return self._forward(x)
 
     def _forward(self, x):
+        if not self.training and ops.EVAL_HALF:  # f16 inference: each block's activation and its max-pool from one apply pass
+            x0, p = self.in_conv(x, pool=True)
+            x1, p = self.down1.maxpool_conv[1](p, pool=True)
+            x2, p = self.down2.maxpool_conv[1](p, pool=True)
+            x3, p = self.down3.maxpool_conv[1](p, pool=True)
+            x4 = self.down4.maxpool_conv[1](p)
+            return [x0, x1, x2, x3, x4]
         if self.training and ops.POOL_FUSE:     # nn.MaxPool2d of each DownBlock fused into the block before it; the two
             x0, p = self.in_conv(x, pool=True)  # gradients of x_i (skip + pooling) are summed in that block's backward
             x1, p = self.down1.maxpool_conv[1](p, pool=True)
@@ -200,8 +215,8 @@ class Decoder(nn.Module):
         # (inside `with ops.fm_rows_half(k):` the k finest maps are handed out as stored, for the row-sparse heads)
         if isinstance(ops.FM_CAST, tuple):
             n_cast = len(feature_map) - ops.FM_CAST[1]
-            return ops.from_half(output), [ops.from_half(f) for f in feature_map[:n_cast]] + feature_map[n_cast:]
-        return ops.from_half(output), ([ops.from_half(f) for f in feature_map] if ops.FM_CAST else feature_map)
+            return ops.logits_out(output), [ops.from_half(f) for f in feature_map[:n_cast]] + feature_map[n_cast:]
+        return ops.logits_out(output), ([ops.from_half(f) for f in feature_map] if ops.FM_CAST else feature_map)
 
 
 class UNet(nn.Module):

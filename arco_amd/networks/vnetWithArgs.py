@@ -12,7 +12,8 @@ nn.BatchNorm3d children are parameter containers).  Forward on channels-last-3d 
   k2 s2 convT = 1x1x1 GEMM to 8*C channels + depth-to-space, then BN+ReLU.
 With ops.ACT_HALF (train_arco_3d --act_dtype f16; BASELINE.json configs[4]) the first layer writes f16 and the whole body runs
 on f16 activations and activation gradients (csrc/conv_h.hip, the *_h entry points; 'batchnorm' only); the logits and the
-feature maps are handed out as fp32.
+feature maps are handed out as fp32.  Inside `with ops.eval_half():` an evaluation-mode forward takes the same f16 route without the
+process-wide switch (arco_amd.eval_surface: act_dtype="f16").
 """
 import torch
 from torch import nn
@@ -226,8 +227,8 @@ class VNet(nn.Module):
         # f16 activation storage (ops.ACT_HALF): the logits and the feature maps leave the f16 region as fp32 - heads, losses
         # and samplers are fp32; gradients come back through the same boundary with the loss scale
         if ops.FM_CAST == 'lowres':      # ops.fm_rows_half: the two full-resolution maps stay f16 for the row-sparse heads
-            return ops.from_half(out), [ops.from_half(f) for f in feature_map[:-2]] + feature_map[-2:]
-        return ops.from_half(out), ([ops.from_half(f) for f in feature_map] if ops.FM_CAST else feature_map)
+            return ops.logits_out(out), [ops.from_half(f) for f in feature_map[:-2]] + feature_map[-2:]
+        return ops.logits_out(out), ([ops.from_half(f) for f in feature_map] if ops.FM_CAST else feature_map)
 
     def forward(self, input, turnoff_drop=False):
         if turnoff_drop:

@@ -468,7 +468,8 @@ _OPEN_HALF_2D = False
 
 class open_half:
     """`with ops.open_half(on):` - a 3x3 convolution of an fp32 IMAGE (<= 4 channels) inside writes f16: the U-Net's first layer
-    opens the f16 region (unetWithArgs.Encoder enters it in training mode only; evaluation stays on the fp32 route)."""
+    opens the f16 region (unetWithArgs.Encoder enters it in training mode under ACT_HALF, and in evaluation mode inside
+    `ops.eval_half()`; evaluation outside that scope stays on the fp32 route)."""
 
     def __init__(self, on=True):
         self.on = bool(on)
@@ -482,11 +483,49 @@ class open_half:
         _OPEN_HALF_2D = self.prev
 
 
+EVAL_HALF = False     # inside `with ops.eval_half():`
+LOGITS_CAST = True    # False inside `with ops.eval_half(logits="stored")`: the networks hand the logits out as the last conv wrote them
+
+
+class eval_half:
+    """`with ops.eval_half():` - F16 INFERENCE, opt-in and scoped: an evaluation-mode forward of the U-Net or of the V-Net
+    (normalization='batchnorm') inside keeps every activation as f16.  The U-Net's Encoder opens the f16 region at in_conv's first
+    layer (fp32 image in, f16 out, as `open_half` does for training), every stage below runs conv_bn_act_eval on f16 tensors, the
+    encoder blocks take the pooled apply pass (arco_bn_act_pool_fwd_h) into a buffer with concat room, the decoder the *_h 1x1
+    conv / upsample; the V-Net takes the route it takes under ACT_HALF.  Logits and feature maps leave as fp32 (from_half);
+    `eval_half(logits="stored")` hands the logits out as the f16 tensor the last convolution wrote (eval_surface.predict_volume
+    (zoom="gpu") reads them with arco_argmax_zoom_back2d_h: no cast pass).  The state before the scope is put back on exit, also when
+    the body raises; ACT_HALF is neither read for the U-Net's eval route nor written.  The f16 and the fp32 weight packs are cached
+    side by side per weight epoch (pack_weight / _pack_half), so a forward after the scope reads the fp32 packs it read before."""
+
+    LOGITS = ("f32", "stored")
+
+    def __init__(self, logits="f32"):
+        if logits not in self.LOGITS:
+            raise ValueError(f"eval_half(logits=...) must be one of {self.LOGITS}, got {logits!r}")
+        self.cast = logits == "f32"
+
+    def __enter__(self):
+        global EVAL_HALF, LOGITS_CAST
+        self.prev = (EVAL_HALF, LOGITS_CAST)
+        EVAL_HALF, LOGITS_CAST = True, self.cast
+        return self
+
+    def __exit__(self, *exc):
+        global EVAL_HALF, LOGITS_CAST
+        EVAL_HALF, LOGITS_CAST = self.prev
+
+
+def logits_out(x):
+    """The logits as a network hands them out: fp32 (from_half), or as stored inside `eval_half(logits="stored")`."""
+    return from_half(x) if LOGITS_CAST else x
+
+
 def use_half(x, taps, ci):
     """Does a convolution of x run on the f16-storage kernels?  Yes when x is f16, or when x is the fp32 one-channel volume
-    entering the V-Net's first 3x3x3 layer in f16 mode (that layer's output opens the f16 region), or the fp32 image entering
-    the U-Net's first 3x3 layer inside `ops.open_half()`."""
-    return _is_half(x) or (ACT_HALF and taps == 27 and ci == 1 and x.dim() == 5) \
+    entering the V-Net's first 3x3x3 layer in f16 mode (ACT_HALF, or inside `ops.eval_half()`; that layer's output opens the f16
+    region), or the fp32 image entering the U-Net's first 3x3 layer inside `ops.open_half()`."""
+    return _is_half(x) or ((ACT_HALF or EVAL_HALF) and taps == 27 and ci == 1 and x.dim() == 5) \
         or (_OPEN_HALF_2D and taps == 9 and ci <= 4 and x.dim() == 4)
 
 
@@ -956,7 +995,8 @@ def _take_cat_buf(y, pool):
 
 def _bn_apply_pool(zr, ldz, nv, h, w, co, mean, istd, gamma, beta, slope, drop_mode, a, ld_a, G):
     """The dropout-free apply pass of a 2-D stage into `a` AND a's 2x2 max-pool (encoder blocks: next DownBlock + decoder skip);
-    returns the pooled tensor.  fp32: one pass; f16 storage: the apply pass and the pooling pass (no pooled apply kernel in f16)."""
+    returns the pooled tensor.  fp32: one pass; f16 storage: the apply pass and the pooling pass (training keeps its two passes; the
+    pooled apply kernel in f16, arco_bn_act_pool_fwd_h, serves the inference route: conv_bn_act_eval(pool=True))."""
     m = nv * h * w
     pooled = new_act_nd(nv, co, (h // 2, w // 2), zr.device, zr.dtype)
     if _is_half(zr):
@@ -1666,8 +1706,10 @@ def upcat(x, skip):
     return UpCatFn.apply(x, skip, buf)
 
 
-def conv_bn_act_eval(x, weight, bias, gamma, beta, running_mean, running_var, slope=0.01, eps=1e-5):
-    """Inference-mode stage (BN uses running statistics); no autograd."""
+def conv_bn_act_eval(x, weight, bias, gamma, beta, running_mean, running_var, slope=0.01, eps=1e-5, cat_room=0, pool=False):
+    """Inference-mode stage (BN uses running statistics); no autograd.
+    pool=True (f16 storage, 2-D: the encoder blocks of the f16 inference route, `ops.eval_half()`): returns (a, maxpool2(a)) from the
+    pooled apply pass (arco_bn_act_pool_fwd_h), `a` written with `cat_room` more channels behind it (a._arco_cat_buf, for upcat)."""
     with torch.no_grad():
         taps = _taps(weight)
         xr, ld, nv, d3, h, w, ci, sp = _geom_nd(x)
@@ -1675,7 +1717,23 @@ def conv_bn_act_eval(x, weight, bias, gamma, beta, running_mean, running_var, sl
         half = use_half(x, taps, ci)
         z, _ = conv_raw(xr, ld, ci, pack_weight(weight, taps, 0, half=_half_pack(half, taps, ci)), co, nv, h, w, taps, bias=bias, d3=d3, sp=sp,
                         half=half)
-        return bn_act_eval(z, gamma, beta, running_mean, running_var, slope, eps)
+        if not pool:
+            if cat_room:
+                raise RuntimeError("arco_amd: conv_bn_act_eval(cat_room=...) comes with pool=True")
+            return bn_act_eval(z, gamma, beta, running_mean, running_var, slope, eps)
+        if not half or d3 != 1:
+            raise RuntimeError("arco_amd: conv_bn_act_eval(pool=True) is the 2-D f16 inference route (the fp32 one pools separately)")
+        global _LAST_CAT_BUF
+        zr, ldz = rows_view(z)
+        a, ld_a = _act_out(nv, co, sp, x.device, zr.dtype, cat_room)
+        pooled = new_act_nd(nv, co, (h // 2, w // 2), x.device, zr.dtype)
+        istd = torch.rsqrt(running_var + eps)
+        _work((2 * nv * h * w + nv * h * w // 4) * co * 2)
+        L.call("arco_bn_act_pool_fwd_h", L.ptr(zr), ldz, nv, h, w, co, L.ptr(running_mean), L.ptr(istd),
+               L.ptr(gamma), L.ptr(beta), float(slope), L.ptr(a), ld_a, L.ptr(pooled), co, 1)
+        if cat_room:
+            a._arco_cat_buf, _LAST_CAT_BUF = _LAST_CAT_BUF, None
+        return a, pooled
 
 
 def bn_act_eval(z, gamma, beta, running_mean, running_var, slope=0.0, eps=1e-5):

@@ -91,7 +91,8 @@ def zoom_nearest(x, out_size):
 def argmax_zoom_back(logits, out_size):
     """int64 [n, x, y] on the device: argmax(softmax(logits, dim=1), dim=1) of [n, C, P0, P1] logits zoomed (order 0) to out_size =
     (x, y).  Any layout of the logits that _contrast.rows_view takes without a copy (channels-last, a channel slice of it) is read in
-    place."""
+    place.  float16 logits (the stored logits of `ops.eval_half(logits="stored")`) go to arco_argmax_zoom_back2d_h, which widens each
+    sampled row in registers: the labels of the fp32 cast of the same logits, without the cast pass."""
     N0, N1 = _out_size(out_size)
     if not torch.is_tensor(logits) or not logits.is_cuda:
         raise TypeError("argmax_zoom_back takes a torch tensor on the GPU")
@@ -100,12 +101,11 @@ def argmax_zoom_back(logits, out_size):
     n, C, P0, P1 = (int(v) for v in logits.shape)
     if C > MAX_CLASSES:
         raise ValueError(f"at most {MAX_CLASSES} classes, got {C}")
-    r, ld = rows_view(logits.detach())
-    if r.dtype != torch.float32:
-        r, ld = r.float().contiguous(), C
+    r, ld = rows_view(logits.detach())                       # float32 or float16 rows (any other dtype arrives as float32)
+    entry = "arco_argmax_zoom_back2d_h" if r.dtype == torch.float16 else "arco_argmax_zoom_back2d"     # f16 rows are read as stored
     out = torch.empty((n, N0, N1), dtype=torch.int64, device=logits.device)
     with torch.cuda.device(logits.device):
-        L.call("arco_argmax_zoom_back2d", L.ptr(r), ld, C, n, P0, P1, N0, N1, _step(P0, N0), _step(P1, N1), L.ptr(out))
+        L.call(entry, L.ptr(r), ld, C, n, P0, P1, N0, N1, _step(P0, N0), _step(P1, N1), L.ptr(out))
     return out
 
 

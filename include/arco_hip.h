@@ -534,6 +534,12 @@ int arco_zoom_nearest2d(const void* src, int S, int n0, int n1, int N0, int N1, 
                         void* stream);
 int arco_argmax_zoom_back2d(const float* X, long ld, int C, int n, int P0, int P1, int N0, int N1, double z0, double z1, int64_t* out,
                             void* stream);
+/*      arco_argmax_zoom_back2d_h: the same on f16 logits rows (the stored logits of the f16 inference route, ops.eval_half(logits="stored")):
+ *      every value is widened to fp32 - exact - and goes through the same arithmetic, so `out` is what arco_argmax_zoom_back2d gives for
+ *      the fp32 cast of the rows, first maximum on ties included.  8-byte loads where ld % 4 == 0 and X is 8-byte aligned, else one value
+ *      at a time.  The same ARCO_ERR_ARG cases.                                                                                     */
+int arco_argmax_zoom_back2d_h(const void* X, long ld, int C, int n, int P0, int P1, int N0, int N1, double z0, double z1, int64_t* out,
+                              void* stream);
 /* ---- V  zoom(order=3) of 2-D evaluation (the reference's test.py:124; csrc/zoom.hip, arco_amd/utils/zoom_gpu.py):
  *      scipy.ndimage.zoom(a, f, order=3) with scipy's defaults (mode='constant', cval=0, prefilter=True, grid_mode=False) of float32
  *      slices, as two steps in float64 without contraction, every operation in the order tests/zoom_cubic_kernel_refs.py restates.
@@ -673,13 +679,22 @@ int arco_cast_f2h(const float* x, long n, float scale, void* y, void* stream);
  *                                (arco_conv3x3_image_mblocks_h of them).
  *   arco_conv3x3_image_wgrad_h:  its weight gradient from the f16 dZ (16 channels) and the fp32 image; ws as arco_wgrad_ws_floats.
  *   arco_maxpool2_*_h / arco_bilinear_*_h: the fp32 entry points of the same name on f16 tensors (C % 8 == 0, rows of whole
- *                                16-byte pieces): fp32 arithmetic, one rounding on store.                                       */
+ *                                16-byte pieces): fp32 arithmetic, one rounding on store.
+ *   arco_bn_act_pool_fwd_h:      arco_bn_act_pool_fwd on f16 tensors (the f16 inference route of the U-Net's encoder blocks): Z is
+ *                                read once, A = lrelu(BN(Z)) is formed in fp32 by arco_bn_act_fwd_h's expression and rounded once,
+ *                                P = the 2x2 maximum of the rounded values - both outputs bit for bit arco_bn_act_fwd_h followed by
+ *                                arco_maxpool2_fwd_h.  lda may exceed C (concat room: the other channels are not touched).  C and
+ *                                the strides multiples of 4, H and W even, the f16 pointers 8-byte and the parameter pointers
+ *                                16-byte aligned; 16-byte lanes where C % 8 == 0 and every row is whole 16-byte pieces.        */
 int arco_conv3x3_image_mblocks_h(int NB, int H, int W, int stat_groups);
 int arco_conv3x3_image_fwd_h(const float* in, long ld_in, int K, const float* Wp, int N, void* out, long ld_out, const float* bias,
                              float* stat_sum, float* stat_sq, int NB, int H, int W, int stat_groups, void* stream);
 int arco_conv3x3_image_wgrad_h(const void* dZ, long ld_dz, int Cout, const float* in, long ld_in, int K, int NB, int H, int W,
                                float* ws, float* dW, int accumulate, void* stream);
 int arco_maxpool2_fwd_h(const void* X, long ldx, int NB, int H, int W, int C, void* Y, long ldy, void* stream);
+int arco_bn_act_pool_fwd_h(const void* Z, long ldz, int NB, int H, int W, int C, const float* mean, const float* istd,
+                           const float* gamma, const float* beta, float slope, void* A, long lda, void* P, long ldp, int groups,
+                           void* stream);
 int arco_maxpool2_bwd_h(const void* X, long ldx, int NB, int H, int W, int C, const void* dY, long ldy, void* dX, long ldo,
                         void* stream);
 int arco_maxpool2_bwd_add_h(const void* X, long ldx, int NB, int H, int W, int C, const void* dY, long ldy, const void* add,

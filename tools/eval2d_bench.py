@@ -12,11 +12,14 @@ Medians after warm-up.  Before anything is timed the two routes are compared: th
 --order 3 adds, per volume, the same case with the cubic-spline zoom of the slices (order=3, the reference's test.py:116-135) on the
 host route and on the gpu route, next to the order-0 gpu route of the same process, and the three kernels of zoom_gpu.zoom_cubic alone
 (the two prefilter passes and the interpolation) next to the bytes each must move and scipy's zoom(order=3) of the same slices.
+--act-dtype f16 adds, per volume, the zoom="gpu" case at act_dtype="f32" and at act_dtype="f16" (the forwards inside ops.eval_half,
+the stored f16 logits read by arco_argmax_zoom_back2d_h), the two alternating in one process, with the calls of library entry points
+one case makes on either route and the network forward of the case's slices alone on either route.
 
 Every step runs in a child process of its own under --step-timeout seconds; the first step that fails or runs out of time ends the
 run (nothing more is started on the GPU after it).
 
-  python tools/eval2d_bench.py [--order 3] [--reps 10 --warmup 3 --kernel-reps 50 --step-timeout 300] [--out eval2d_bench_table.md]
+  python tools/eval2d_bench.py [--order 3] [--act-dtype f16] [--reps 10 --warmup 3 --kernel-reps 50 --step-timeout 300] [--out eval2d_bench_table.md]
 --out writes the tables and the line under them, nothing else.  profiles/eval2d_gpu_notes.md quotes such tables inside notes written
 by hand; the tool refuses to overwrite that file."""
 import argparse
@@ -192,11 +195,56 @@ def step_kernels3(shape_name, args):
                 cols_bytes=(4 + 8) * n, rows_bytes=(8 + 8) * n, interp_bytes=8 * n + 4 * S * PATCH[0] * PATCH[1], lines_cols=S * y, lines_rows=S * x)
 
 
-STEPS = {"case": step_case, "kernels": step_kernels, "case3": step_case3, "kernels3": step_kernels3}
+def step_caseh(shape_name, args):
+    """One zoom="gpu" case at act_dtype="f32" and at "f16", alternating; the library entry points one case calls; the forward alone."""
+    import torch
+    import arco_amd._lib as L
+    from arco_amd import eval_surface, ops
+    img, lab = make_case(SHAPES[shape_name])
+    net = _net()
+    routes = {"f32": dict(zoom="gpu", act_dtype="f32"), "f16": dict(zoom="gpu", act_dtype="f16")}
+    maps = {k: eval_surface.predict_volume(img, net, PATCH, **kw) for k, kw in routes.items()}
+    metrics = {k: eval_surface.test_single_volume(img, lab, net, CLASSES, PATCH, surface="gpu", **kw) for k, kw in routes.items()}
+    calls, real_call = {}, L.call
+    for k, kw in routes.items():                       # counted outside the timed runs
+        n = [0]
+
+        def counting(name, *a, _n=n):
+            _n[0] += 1
+            return real_call(name, *a)
+        L.call = counting
+        try:
+            eval_surface.test_single_volume(img, lab, net, CLASSES, PATCH, surface="gpu", **kw)
+        finally:
+            L.call = real_call
+        calls[k] = n[0]
+    ts = {k: [] for k in routes}
+    for i in range(args.warmup + args.reps):
+        for k, kw in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eval_surface.test_single_volume(img, lab, net, CLASSES, PATCH, surface="gpu", **kw)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                ts[k].append(time.perf_counter() - t0)
+    inp = torch.randn((img.shape[0], 1) + PATCH, device="cuda")
+    with torch.no_grad():
+        t_net32 = event_ms(lambda: net(inp), args.kernel_reps, args.warmup)
+        with ops.eval_half(logits="stored"):
+            t_net16 = event_ms(lambda: net(inp), args.kernel_reps, args.warmup)
+    res = dict(shape=shape_name, net32=t_net32, net16=t_net16, calls32=calls["f32"], calls16=calls["f16"],
+               labels_differ=float((maps["f32"] != maps["f16"]).float().mean()), dice32=[float(m[0]) for m in metrics["f32"]],
+               dice16=[float(m[0]) for m in metrics["f16"]], dev=torch.cuda.get_device_name(0))
+    for k in routes:
+        res[k], res[k + "_min"] = statistics.median(ts[k]) * 1e3, min(ts[k]) * 1e3
+    return res
 
 
-def steps(order=0):
-    for kind in ("case", "kernels") + (("case3", "kernels3") if order == 3 else ()):
+STEPS = {"case": step_case, "kernels": step_kernels, "case3": step_case3, "kernels3": step_kernels3, "caseh": step_caseh}
+
+
+def steps(order=0, act_dtype="f32"):
+    for kind in ("case", "kernels") + (("case3", "kernels3") if order == 3 else ()) + (("caseh",) if act_dtype == "f16" else ()):
         for s in SHAPES:
             yield "%s|%s" % (kind, s)
 
@@ -213,6 +261,7 @@ def main():
     ap.add_argument("--kernel-reps", type=int, default=50)
     ap.add_argument("--step-timeout", type=float, default=300.0, help="seconds for each step (a child process of its own)")
     ap.add_argument("--order", type=int, default=0, choices=(0, 3), help="3: also the order-3 (cubic-spline) case and kernel rows")
+    ap.add_argument("--act-dtype", default="f32", choices=("f32", "f16"), help="f16: also the zoom=\"gpu\" case at act_dtype f32 and f16")
     ap.add_argument("--out", default=None, help="also write the tables to this file (not profiles/eval2d_gpu_notes.md)")
     ap.add_argument("--step", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -220,8 +269,8 @@ def main():
         return run_step(args.step, args)
     if args.out and os.path.basename(args.out) == "eval2d_gpu_notes.md":
         raise SystemExit("eval2d_bench: profiles/eval2d_gpu_notes.md is written by hand around the tables of this tool; give --out another file")
-    case_rows, kernel_rows, case3_rows, kernel3_rows = [], [], [], []
-    for name in steps(args.order):
+    case_rows, kernel_rows, case3_rows, kernel3_rows, caseh_rows = [], [], [], [], []
+    for name in steps(args.order, args.act_dtype):
         cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--reps", str(args.reps), "--warmup", str(args.warmup),
                "--kernel-reps", str(args.kernel_reps)]
         try:
@@ -234,7 +283,11 @@ def main():
             print(p.stdout)
             raise SystemExit("eval2d_bench: step %r failed with exit status %d; nothing more is started" % (name, p.returncode))
         r = found[0]
-        if name.startswith("case3"):
+        if name.startswith("caseh"):
+            caseh_rows.append(r)
+            print("%-11s zoom=gpu per case: act_dtype f32 %8.2f ms, f16 %8.2f ms; net forward f32 %.3f ms, f16 %.3f ms; entry calls %d / %d" %
+                  (r["shape"], r["f32"], r["f16"], r["net32"], r["net16"], r["calls32"], r["calls16"]), flush=True)
+        elif name.startswith("case3"):
             case3_rows.append(r)
             print("%-11s order 3 per case: zoom=host %8.2f ms, zoom=gpu %8.2f ms; order 0 zoom=gpu %8.2f ms; net forward %.2f ms" %
                   (r["shape"], r["host3"], r["gpu3"], r["gpu0"], r["net"]), flush=True)
@@ -289,6 +342,21 @@ def main():
                   ", ".join("%s %s" % (r["shape"], "yes" if r["same_map"] else "NO") for r in case3_rows),
                   ", ".join("%s %s" % (r["shape"], "yes" if r["same_metrics"] else "NO") for r in case3_rows),
                   ", ".join("%s %s" % (r["shape"], "yes" if r["differs_from_order0"] else "no") for r in case3_rows)))
+    if args.act_dtype == "f16":
+        lines = ["", "| Volume | zoom=\"gpu\", act_dtype=\"f32\" | zoom=\"gpu\", act_dtype=\"f16\" | f32 / f16 | entry-point calls per case, f32 | f16 | "
+                 "net forward of the case, f32 | f16 |", "|---|---|---|---|---|---|---|---|"]
+        for r in caseh_rows:
+            lines.append("| %s | %.2f ms | %.2f ms | %.2fx | %d | %d | %.3f ms | %.3f ms |" %
+                         (r["shape"], r["f32"], r["f16"], r["f32"] / r["f16"], r["calls32"], r["calls16"], r["net32"], r["net16"]))
+        table += "\n" + "\n".join(lines)
+        note += ("\n\nact_dtype: the two routes alternate in one process (fastest runs, f32 / f16: %s).  Entry-point calls: the calls of "
+                 "library entry points (_lib.call) one test_single_volume makes, counted in a run of its own - an entry point may launch "
+                 "more than one kernel, and torch's own launches (the rsqrt of the running variances, copies, the cat of the fp32 eval "
+                 "route) are not in it.  Net forward: the eval-mode forward of the case's slices alone, median of %d between device "
+                 "events.  Share of the label map that differs between the two routes: %s; dice per class f32 / f16: %s." %
+                 ("; ".join("%s %.2f / %.2f ms" % (r["shape"], r["f32_min"], r["f16_min"]) for r in caseh_rows), args.kernel_reps,
+                  ", ".join("%s %.2e" % (r["shape"], r["labels_differ"]) for r in caseh_rows),
+                  "; ".join("%s %s / %s" % (r["shape"], ["%.4f" % d for d in r["dice32"]], ["%.4f" % d for d in r["dice16"]]) for r in caseh_rows)))
     print(table + "\n\n" + note)
     if args.out:
         with open(args.out, "w") as f:
