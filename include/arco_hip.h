@@ -193,8 +193,16 @@ int arco_conv_fwd(const float* in, long ld_in, int K, const float* Wp, int N, fl
 int arco_conv3d_fwd(const float* in, long ld_in, int K, const float* Wp, int N, float* out, long ld_out,
                     const float* bias, const float* residual, long ld_res, float* stat_sum, float* stat_sq, int taps,
                     int NV, int D3, int H, int W,
-                    int stat_groups /* BN groups: volumes [g*NV/G,..) feed stat slabs [g*nmb/G,..); 1 = one batch */, int mma /* 0: fp32 MFMA (default, parity); 1 / 2: 3x3x3 operands rounded to f16 / bf16 in registers, fp32 accumulate
-                               (BASELINE.json configs[4] "fp16 MFMA conv"; tolerance 1e-2; opt-in) */,
+                    int stat_groups /* BN groups: volumes [g*NV/G,..) feed stat slabs [g*nmb/G,..); 1 = one batch */, int mma /* 0: fp32 MFMA (default, parity); 1 / 2: the operands of the 3x3x3 convolutions and 1x1x1 GEMMs
+                               rounded to f16 / bf16 in registers (BASELINE.json configs[4] "fp16 MFMA conv"; tolerance 1e-2; opt-in), on
+                               the plain fp32 pack (mode 0 / 1).  Contract, held bit for bit by tests/test_mma12_kernels_gpu.py: BOTH
+                               operands rounded to nearest even - f16 with gradual underflow (subnormal operands are kept) and overflow
+                               to +-inf (65520 and above become infinity, not 65504; inf * 0 = NaN follows) -, the products exact (22 /
+                               16 bits), fp32 accumulation, bias and residual unrounded in the fp32 epilogue: the result is the fp32
+                               convolution of the rounded operands.  Shapes that run the fp32 arithmetic of mma 0 whatever the mode: taps
+                               9 (3x3 per plane, any D3), K % 4 != 0 or ld_in % 4 != 0 (the scalar-load form), the one-channel 3x3x3
+                               volume (conv3d_image_kernel<3>); the streaming 1x1 kernels are not taken in these modes. 3: split-bf16
+                               (the mode | 2 pack); 4: f16 activation storage (conv_h.hip, the mode | 4 pack) */,
                     void* stream);
 int arco_conv3d_wgrad(const float* dZ, long ld_dz, int Cout, const float* in, long ld_in, int Cin, int taps, int NV,
                       int D3, int H, int W, float* ws, float* dW, int accumulate,

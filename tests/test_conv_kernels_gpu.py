@@ -45,9 +45,9 @@ rule refuses Npad < 208 at any tile threshold: the case asserts igemm_kernel<1,3
 picks at no plane width of this file and only a forced ARCO_CONV3D_FL_CFG reaches (tests/test_conv3d_fl_gpu.py runs each of them).  The
 largest 3x3x3 tiles (50176 .. 65536 voxels) run the fixed and the wide kind only; their smaller siblings run all four.
 Out of scope: the weight-gradient kernels, the BatchNorm / GroupNorm family (held to float64 kernel by kernel in
-tests/test_norm_kernels_gpu.py), conv_h.hip (mma 4: held to float64 route by route in tests/test_hconv_kernels_gpu.py) and the
-opt-in mma 1 / 2, arco_conv3d_fwd_pro
-(tests/test_block_fuse_gpu.py ties it bit for bit to the two-pass route that this file anchors)."""
+tests/test_norm_kernels_gpu.py), conv_h.hip (mma 4: held to float64 route by route in tests/test_hconv_kernels_gpu.py), the
+opt-in mma 1 / 2 (held bit for bit to a float64 convolution of the rounded operands in tests/test_mma12_kernels_gpu.py) and
+arco_conv3d_fwd_pro (tests/test_block_fuse_gpu.py ties it bit for bit to the two-pass route that this file anchors)."""
 import contextlib
 import struct
 

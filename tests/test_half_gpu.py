@@ -483,7 +483,8 @@ def test_head_gemms_on_f16_operands():
     """ops.HEAD_MMA = 1 (train_arco_3d --act_dtype f16, --head_mma auto): a 1x1x1 convolution over an fp32 map - FeatureExtractor_3d /
     q_representation (model_3D.py:37-63, train_arco_3d.py:206-209) - rounds its operands to f16 in registers (bf16 for the data
     gradient's operands), fp32 accumulate: output and input gradient within 2e-3 of the fp32-accurate GEMM (K = 448: 1e-2 budget of
-    BASELINE configs[4] with room), not bit-equal to it (the reduced-precision kernel really ran), weight gradient fp32."""
+    BASELINE configs[4] with room), not bit-equal to it (the reduced-precision kernel really ran), weight gradient fp32.  The modes themselves are held bit for bit to a
+    float64 convolution of the rounded operands, tile by tile, in tests/test_mma12_kernels_gpu.py."""
     from arco_amd import ops
     dev = "cuda:0"
     torch.manual_seed(0)
