@@ -160,6 +160,8 @@ _SIGS = {
     "arco_ema": [_P, _P, _L, _F, _P],
     "arco_ingest_slices": [_P, _P, _L, _P, _L, _P, _I, _I, _I, _P, _P, _P],
     "arco_ingest_volumes": [_P, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P],
+    "arco_gray_jitter_planes": [_P, _L, _L, _I, _I, _I, _L, _L, _L, _L, _P, _P],
+    "arco_blur_planes": [_P, _L, _L, _I, _I, _I, _L, _L, _L, _L, _F, _P, _P, _P],
 }
 _QUERIES = {   # plain host helpers returning sizes
     "arco_proto_ws_floats": ([_L, _I, _I], _L),
@@ -192,6 +194,8 @@ _QUERIES = {   # plain host helpers returning sizes
     "arco_surface_sp_ws_bytes": ([_I, _I, _I, _I], _L),
     "arco_cc_ws_bytes": ([_I, _I, _I], _L),
     "arco_cc_value_ws_bytes": ([_I, _I, _I, _I], _L),
+    "arco_jit_record_bytes": ([], _L),
+    "arco_blur_planes_ws_bytes": ([_L, _I, _I, _I], _L),
     # host-side native sampler replay (no GPU work)
     "arco_grid_sample": ([_P, _L, _L, _L, _I, _I, _P], _L),
     "arco_randint": ([_P, _L, _L, _L, _P], _L),

@@ -10,7 +10,8 @@ it is nearest-neighbour or an index map, and none of its random draws looks at p
     calls, same order) and returns the case index plus the drawn parameters, a row of 16 float64 / 8 int64;
   * `stepper.paired_loaders` wraps them as it wraps the host datasets (the samplers, the loaders' base-seed draws and the doubling
     of the labeled set are the same code), and `GpuBank.slices` / `.volumes` turn a collated batch of rows into the batch the host path would
-    have produced, bit for bit, with one kernel launch.
+    have produced, bit for bit, with one kernel launch;
+  * `bank_loader` does the same for the pre-trainers' single loader over a TwoStreamBatchSampler (pretrain_2D / pretrain_3D).
 
 Casting at upload changes nothing: nearest resampling and zero fill commute with astype(float32) / astype(uint8)."""
 import random
@@ -270,3 +271,15 @@ def bank_loaders(host_loaders, paired_loaders, batch_size, device, generator=Non
     twins = [bank.descriptors(ds.transform) for bank, ds in zip(banks, sets)]
     loaders = paired_loaders(*twins, batch_size, generator)
     return tuple(BankLoader(ld, bank, tw.patch_size, labels=lab) for ld, bank, tw, lab in zip(loaders, banks, twins, (True, unlabeled_labels)))
+
+
+def bank_loader(host_loader, device):
+    """The loader of --gpu_ingest 1 for the pre-trainers' shape - ONE host loader over the whole list with
+    batch_sampler=TwoStreamBatchSampler: a bank of the loader's dataset, the descriptor twin of that dataset and the SAME sampler object
+    around the twin.  Every sample of a batch may be a labeled one, so the batches always carry labels."""
+    from torch.utils.data import DataLoader
+    ds = host_loader.dataset
+    bank = GpuBank.from_dataset(ds, device)
+    twin = bank.descriptors(ds.transform)
+    loader = DataLoader(twin, batch_sampler=host_loader.batch_sampler, num_workers=0, pin_memory=host_loader.pin_memory)
+    return BankLoader(loader, bank, twin.patch_size, labels=True)

@@ -6,7 +6,8 @@ KL-divergence-to-queue terms (latent vector, patch-wise output embeddings; pretr
 Same flag table (names, defaults), same loss arithmetic, same generator consumption as the reference; both U-Nets run on
 the HIP kernels (arco_amd.ops), the optimizer is torch.optim.SGD(momentum=0.9, weight_decay=1e-4) on flat buffers
 (arco_sgd_momentum).  `--synthetic 1` replaces the slice loader with seeded ACDC-shaped tensors (no dataset ships with the
-reference)."""
+reference); `--gpu_ingest 1` keeps the dataset in device memory and runs the student transform as HIP kernels, with the host
+route's random draws (dataloaders/gpu_ingest.py, dataloaders/stage1_aug.py)."""
 import argparse
 import logging
 import os
@@ -57,6 +58,9 @@ def build_parser():
     p.add_argument('--synthetic', type=int, default=0, help='1: seeded ACDC-shaped tensors instead of the slice loader')
     p.add_argument('--save_every', type=int, default=1000, help='checkpoint interval (the reference hard-codes 1000)')
     p.add_argument('--snapshot_path', type=str, default='', help='overrides ../model/<exp>_<labeled_num>_labeled<suffix>/<model>')
+    p.add_argument('--gpu_ingest', type=int, default=0, choices=[0, 1],
+                   help='1: the student transform as HIP kernels and, with --synthetic 0, the dataset in device memory, every batch one '
+                        'launch (dataloaders/gpu_ingest.py, dataloaders/stage1_aug.py); 0: the host loader and the tensor-op transform')
     return p
 
 
@@ -197,13 +201,21 @@ def build_loader(args):
     return DataLoader(db, batch_sampler=sampler, num_workers=0, pin_memory=True)
 
 
-def train(args, snapshot_path):
+def run_training(args, snapshot_path, stepper_cls, transform_student, build_loader, synthetic_batch, synthetic_per_epoch):
+    """The training loop of either pre-trainer (pretrain_2D.py:189-291, pretrain_3D.py:163-260).  --gpu_ingest 1 swaps the student
+    transform for its device twin (same draws, one launch per op) and, with a dataset, the host loader for a bank loader (the
+    dataset in device memory, the same sampler, every batch one launch, equal to the host loader's bit for bit)."""
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    stepper = PretrainStep2D(args, dev)
-    transform_student = make_transform_student()
+    stepper = stepper_cls(args, dev)
     loader = None if args.synthetic else build_loader(args)
-    per_epoch = 50 if args.synthetic else len(loader)
+    if getattr(args, "gpu_ingest", 0):
+        from .dataloaders import gpu_ingest, stage1_aug
+        transform_student = stage1_aug.device_transform(transform_student)
+        if loader is not None:
+            loader = gpu_ingest.bank_loader(loader, dev)
+            logging.info("gpu ingest: {} cases, {:.1f} MB of device memory".format(loader.bank.n_cases, loader.bank.nbytes / 1e6))
+    per_epoch = synthetic_per_epoch if args.synthetic else len(loader)
     logging.info("{} iterations per epoch".format(per_epoch))
     max_epoch = args.max_iterations // per_epoch + 1
     for epoch_num in range(max_epoch):
@@ -224,6 +236,10 @@ def train(args, snapshot_path):
         if stepper.iter_num >= args.max_iterations:
             break
     return "Training Finished!"
+
+
+def train(args, snapshot_path):
+    return run_training(args, snapshot_path, PretrainStep2D, make_transform_student(), build_loader, synthetic_batch, 50)
 
 
 def main(argv=None):

@@ -65,32 +65,7 @@ def build_loader(args):
 
 
 def train(args, snapshot_path):
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
-    stepper = PretrainStep3D(args, dev)
-    transform_student = make_transform_student()
-    loader = None if args.synthetic else build_loader(args)
-    per_epoch = 20 if args.synthetic else len(loader)
-    logging.info("{} iterations per epoch".format(per_epoch))
-    max_epoch = args.max_iterations // per_epoch + 1
-    for epoch_num in range(max_epoch):
-        batches = (synthetic_batch(args.batch_size, args.patch_size, args.num_classes, args.seed + 1000 * epoch_num + i)
-                   for i in range(per_epoch)) if args.synthetic else loader
-        for sampled_batch in batches:
-            sampled_batch = {'image': sampled_batch['image'].to(dev, non_blocking=True),
-                             'label': sampled_batch['label'].to(dev, non_blocking=True)}
-            student, teacher = student_teacher_batches(sampled_batch, args.combinations, transform_student)
-            loss = stepper.step(student['image'], student['label'], teacher['image'])
-            t = stepper.last_terms
-            logging.info('iteration %d : loss : %f, loss_ce: %f, loss_dice: %f, loss_latent: %f, loss_output: %f' %
-                         (stepper.iter_num, loss.item(), t['ce'].item(), t['dice'].item(), t['latent'].item(), t['output'].item()))
-            if stepper.iter_num % args.save_every == 0:
-                stepper.save(snapshot_path)
-            if stepper.iter_num >= args.max_iterations:
-                break
-        if stepper.iter_num >= args.max_iterations:
-            break
-    return "Training Finished!"
+    return P2.run_training(args, snapshot_path, PretrainStep3D, make_transform_student(), build_loader, synthetic_batch, 20)
 
 
 def main(argv=None):

@@ -719,6 +719,22 @@ int arco_ingest_slices(const float* bank_img, const unsigned char* bank_lab, lon
                        const double* desc, int B, int H, int W, float* out_img, long* out_lab, void* stream);
 int arco_ingest_volumes(const float* bank_img, const unsigned char* bank_lab, long bank_elems, const long* table, long n_cases,
                         const long* desc, int B, int X, int Y, int Z, float* out_img, long* out_lab, void* stream);
+/* The student transform of stage-1 pre-training (pretrain_2D / pretrain_3D --gpu_ingest 1; csrc/stage1_aug.hip,
+ * arco_amd/dataloaders/stage1_aug.py) on PLANES of one fp32 buffer of n_elems elements: plane p = (j, t) = (p / T, p % T) starts at element
+ * j * s_img + t * s_t, pixel (r, c) is r * s_row + c * s_col further on (2-D [B,1,H,W]: T = 1, s_row = W, s_col = 1; 3-D [B,1,X,Y,Z],
+ * planes [j,0,:,:,t]: T = Z, s_t = 1, s_row = Y * Z, s_col = Z).  Planes p >= n_planes are not touched.
+ * arco_gray_jitter_planes: torchvision's tensor-mode ColorJitter on one-channel planes, in place; recs = n_planes records
+ *   {int order[4]; float fb, fc;} (arco_jit_record_bytes) in DEVICE memory; op 0: x = clamp(x * fb, 0, 1), op 1: x = clamp(x * fc +
+ *   (1 - fc) * mean, 0, 1) with the plane's mean summed in float64 in a fixed order (no atomics), ops 2 / 3 nothing; no contraction.
+ * arco_blur_planes: Pillow's GaussianBlur of trunc(clamp(x * 255)) with ONE fractional box radius in [0, 1) for all planes (anything
+ *   else: ARCO_ERR_UNSUPPORTED).  out != null: out [n_planes,H,W] fp32 = byte / 255, apart from data.  out == null: in place,
+ *   data = (float)byte, blurred into the scratch ws (arco_blur_planes_ws_bytes) and stored back by a second launch. */
+long arco_jit_record_bytes(void);
+int arco_gray_jitter_planes(float* data, long n_elems, long n_planes, int T, int H, int W, long s_img, long s_t, long s_row, long s_col,
+                            const void* recs, void* stream);
+long arco_blur_planes_ws_bytes(long n_planes, int T, int H, int W);
+int arco_blur_planes(float* data, long n_elems, long n_planes, int T, int H, int W, long s_img, long s_t, long s_row, long s_col, float radius,
+                     float* out, void* ws, void* stream);
 
 #ifdef __cplusplus
 }
