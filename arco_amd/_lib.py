@@ -162,6 +162,8 @@ _SIGS = {
     "arco_ingest_volumes": [_P, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P],
     "arco_gray_jitter_planes": [_P, _L, _L, _I, _I, _I, _L, _L, _L, _L, _P, _P],
     "arco_blur_planes": [_P, _L, _L, _I, _I, _I, _L, _L, _L, _L, _F, _P, _P, _P],
+    "arco_patch_pool_fwd": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "arco_patch_pool_bwd": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
 }
 _QUERIES = {   # plain host helpers returning sizes
     "arco_proto_ws_floats": ([_L, _I, _I], _L),

@@ -40,7 +40,8 @@ class PretrainStep3D(P2.PretrainStep2D):
         return ISD_3d(K=args.K, m=0.99, Ts=args.T_s, Tt=args.T_t, num_classes=args.num_classes,
                       latent_pooling_size=args.latent_pooling_size, latent_feature_size=args.latent_feature_size,
                       output_pooling_size=args.output_pooling_size, train_encoder=args.train_encoder,
-                      train_decoder=args.train_decoder, patch_size=getattr(args, "head_patch", 20))
+                      train_decoder=args.train_decoder, patch_size=getattr(args, "head_patch", 20),
+                      patch_heads=getattr(args, "patch_heads", "torch"))
 
 
 def synthetic_batch(b, patch, n_cls, seed):

@@ -40,13 +40,47 @@ def _pool_size(pool_layer):
     return o if isinstance(o, int) else o[0]
 
 
-def patch_heads(x, patch, head, predictor):
+class PatchPoolFn(torch.autograd.Function):
+    """adaptive_avg_pool{2,3}d(., pool) of every patch of the patch / 2-stride grid of x [B, C, n...] as one kernel each way
+    (csrc/patch_pool.hip): [P, B, C, pool...], patch number first, the layout torch.cat of the per-patch results has.  Linear, so
+    the backward needs the geometry alone: no tensor is saved."""
+
+    @staticmethod
+    def forward(ctx, x, patch, pool):
+        from . import _lib as L
+        L.require_gpu(x)
+        if x.dtype != torch.float32 or x.dim() not in (4, 5):
+            raise ValueError(f"PatchPoolFn: an fp32 [B, C, n...] map with 2 or 3 spatial axes, got {x.dtype} {tuple(x.shape)}")
+        x = x.contiguous()
+        nd, n = x.dim() - 2, tuple(x.shape[2:])
+        step = max(int(patch) // 2, 1)
+        P = 1
+        for s in n:
+            P *= max((s - patch) // step + 1, 0)          # 0: no patch fits; the entry point refuses the empty output
+        y = torch.empty((P, x.shape[0], x.shape[1]) + (int(pool),) * nd, dtype=torch.float32, device=x.device)
+        ctx.geom = (nd, x.shape[0], x.shape[1]) + n + (1,) * (3 - nd) + (int(patch), int(pool))
+        L.call("arco_patch_pool_fwd", L.ptr(x), *ctx.geom, L.ptr(y))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import _lib as L
+        nd, B, C = ctx.geom[:3]
+        gy = gy.contiguous()
+        gx = torch.empty((B, C) + tuple(ctx.geom[3:3 + nd]), dtype=torch.float32, device=gy.device)
+        L.call("arco_patch_pool_bwd", L.ptr(gy), *ctx.geom, L.ptr(gx))
+        return gx, None, None
+
+
+def patch_heads(x, patch, head, predictor, route="torch"):
     """predictor(head(x[..., i:i+p, j:j+p(, k:k+p)])) for every patch of the p/2-stride grid, in the reference's loop
     order (first spatial axis outermost; model_2D.py:263-268, model_3D.py:355-359).  The head is adaptive average pooling
     followed by 1x1 convolutions: when the pooling windows tile the patch stride, the pooled grid of the WHOLE map is
     computed once (avg_pool with the same windows), the pointwise layers run once on it, and a patch is a window of that
     grid - the same values, hundreds of small launches less (700 patches per volume in 3-D); otherwise the patches are
-    taken one by one like the reference."""
+    taken one by one like the reference.
+    route="gpu": one PatchPoolFn call pools every patch, whatever the patch and pooling sizes, the pointwise layers run once on the
+    [P * B, C, pool...] tensor, and that STACKED tensor is returned (torch.cat of the list above, without the cat)."""
     nd = x.dim() - 2
     conv = F.conv2d if nd == 2 else F.conv3d
     proj = _unwrap(head).proj
@@ -55,6 +89,14 @@ def patch_heads(x, patch, head, predictor):
     step = patch // 2
     starts = [range(0, x.shape[2 + d] - patch + 1, step) for d in range(nd)]
     import itertools
+    if route == "gpu":
+        g = PatchPoolFn.apply(x, patch, pool_out)
+        g = g.reshape((-1,) + tuple(g.shape[2:]))
+        for l in layers:
+            g = conv(g, l.weight, l.bias)
+        return g
+    if route != "torch":
+        raise ValueError(f"patch_heads: route is 'torch' or 'gpu', got {route!r}")
     if patch % pool_out == 0 and step % (patch // pool_out) == 0:
         w = patch // pool_out
         crop = tuple(slice(0, (x.shape[2 + d] // w) * w) for d in range(nd))
@@ -101,11 +143,14 @@ def isd_forward(isd, im_q, im_k=None, Ts=None, Tt=None):
         ema_output = ema_output[reverse_ids]
     queue = isd.queue.clone().detach()
     queue_mask = isd.queue_mask.clone().detach().transpose(0, 1).contiguous()
-    stu = patch_heads(outputs, isd.patch_size, isd.q_outputs_head, isd.outputs_predictor)
-    tea = patch_heads(ema_output, isd.patch_size, isd.k_outputs_head, None)
-    shp = tuple(stu[0].shape[1:])
-    stu = torch.cat(stu).reshape(batch_size, -1, *shp).contiguous()
-    tea = torch.cat(tea).reshape(batch_size, -1, *shp).contiguous()
+    route = getattr(isd, "patch_heads", "torch")
+    stu = patch_heads(outputs, isd.patch_size, isd.q_outputs_head, isd.outputs_predictor, route)
+    tea = patch_heads(ema_output, isd.patch_size, isd.k_outputs_head, None, route)
+    stu = stu if torch.is_tensor(stu) else torch.cat(stu)          # route "gpu" returns the patches stacked already
+    tea = tea if torch.is_tensor(tea) else torch.cat(tea)
+    shp = tuple(stu.shape[1:])
+    stu = stu.reshape(batch_size, -1, *shp).contiguous()
+    tea = tea.reshape(batch_size, -1, *shp).contiguous()
     lat_k = mlp(isd.k_latent_head, ema_latent_vector)
     lat_q = mlp(isd.q_latent_head, latent_vector)
     for l in _unwrap(isd.latent_predictor):

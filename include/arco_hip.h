@@ -736,6 +736,19 @@ long arco_blur_planes_ws_bytes(long n_planes, int T, int H, int W);
 int arco_blur_planes(float* data, long n_elems, long n_planes, int T, int H, int W, long s_img, long s_t, long s_row, long s_col, float radius,
                      float* out, void* ws, void* stream);
 
+/* The patch-wise pooling of the stage-1 output heads (pretrain_2D / pretrain_3D --patch_heads gpu; csrc/patch_pool.hip, arco_amd/stage1.py).
+ * nd = 2: x [B,C,n0,n1] (n2 ignored), nd = 3: x [B,C,n0,n1,n2], fp32 contiguous.  On every spatial axis the patches start at 0, step,
+ * 2 * step, ... while start + patch <= n, step = patch / 2; patch number p counts the first spatial axis outermost.  Cell i of a patch
+ * covers the local coordinates [floor(i * patch / pool), ceil((i + 1) * patch / pool)) (adaptive average pooling; pool need not divide
+ * patch and may exceed it).
+ * fwd: y [P,B,C,pool,pool(,pool)] = the window's fp32 sum (axis 0 outermost, ascending) divided once by its element count.
+ * bwd: gx [B,C,n...] = per voxel the fp32 sum of gy / count(cell) over the (patch, cell) tuples whose window holds it, nested loops
+ *   p0, i0, p1, i1, p2, i2 from the outermost, all ascending; 0 where no patch covers the voxel; every element of gx is written.
+ * No atomics: two runs give the same bits.  ARCO_ERR_ARG before any launch for nd outside {2, 3}, patch < 2, pool < 1, B or C < 1, an
+ * axis shorter than patch, or a null pointer. */
+int arco_patch_pool_fwd(const float* x, int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, float* y, void* stream);
+int arco_patch_pool_bwd(const float* gy, int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, float* gx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
