@@ -164,6 +164,9 @@ _SIGS = {
     "arco_blur_planes": [_P, _L, _L, _I, _I, _I, _L, _L, _L, _L, _F, _P, _P, _P],
     "arco_patch_pool_fwd": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "arco_patch_pool_bwd": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "arco_patch_head_fwd": [_P] + [_I] * 9 + [_P] * 8 + [_I] * 4 + [_P, _P, _P],
+    "arco_patch_head_bwd": [_P, _P] + [_I] * 9 + [_P] * 8 + [_I] * 4 + [_P, _P, _P],
+    "arco_patch_head_wgrad_finish": [_P] + [_I] * 9 + [_I] * 4 + [_P] * 8 + [_P],
 }
 _QUERIES = {   # plain host helpers returning sizes
     "arco_proto_ws_floats": ([_L, _I, _I], _L),
@@ -198,6 +201,7 @@ _QUERIES = {   # plain host helpers returning sizes
     "arco_cc_value_ws_bytes": ([_I, _I, _I, _I], _L),
     "arco_jit_record_bytes": ([], _L),
     "arco_blur_planes_ws_bytes": ([_L, _I, _I, _I], _L),
+    "arco_patch_head_ws_bytes": ([_I] * 13, _L),
     # host-side native sampler replay (no GPU work)
     "arco_grid_sample": ([_P, _L, _L, _L, _I, _I, _P], _L),
     "arco_randint": ([_P, _L, _L, _L, _P], _L),

@@ -1,28 +1,14 @@
 // The patch-wise pooling of the stage-1 output heads (arco_amd/stage1.py patch_heads(route="gpu"), pretrain_2D / pretrain_3D --patch_heads gpu):
 //   arco_patch_pool_fwd   x [B, C, n...] -> y [P, B, C, pool...]: adaptive average pooling of every patch of the patch / 2-stride grid
 //   arco_patch_pool_bwd   gy [P, B, C, pool...] -> gx [B, C, n...]: its adjoint, as a gather
-// Geometry, the same on every spatial axis d (nd = 2 or 3): the patches start at 0, step, 2 * step, ... while start + patch <= n[d], with
-// step = patch / 2, np[d] = (n[d] - patch) / step + 1 of them; patch number p = (p0 * np[1] + p1) * np[2] + p2 (the first spatial axis
-// outermost, the heads' loop order).  Cell i of a patch covers the local coordinates [floor(i * patch / pool), ceil((i + 1) * patch / pool)),
-// the tensor library's adaptive-pooling windows: they overlap when pool does not divide patch, and repeat when pool > patch.
-// A 2-D call runs the 3-D code with a leading axis of one voxel, one patch and one cell of length one: the same sums in the same order.
+// The geometry (patch grid, cell windows, patch numbering) is patch_geom.h's, shared with patch_head.hip.
 //
 // One thread per output element, plain loops, no atomics and no cross-lane sums: two runs give the same bits.  Every float operation
 // rounds on its own (no fused multiply-add), so that tests/patch_pool_refs.py can state the arithmetic element by element.
 #pragma clang fp contract(off)
-#include "common.h"
+#include "patch_geom.h"
 
 namespace {
-
-#define PP_THREADS 256
-#define PP_MAX_BLOCKS 4096
-#define PP_MAX_SIDE 32768            // patch, pool: local coordinate * pool stays inside an int
-
-struct Axis { int n, np, patch, step, pool; };
-struct Geom { Axis a[3]; int B, C; };
-
-__host__ __device__ inline int win_lo(const Axis& a, int i) { return (int)((long)i * a.patch / a.pool); }
-__host__ __device__ inline int win_hi(const Axis& a, int i) { return (int)(((long)(i + 1) * a.patch + a.pool - 1) / a.pool); }
 
 // y[p, b, c, i0, i1, i2] = (sum of the window, axis 0 outermost, every axis ascending, starting from 0.f) / (float)(window elements)
 __global__ __launch_bounds__(PP_THREADS) void patch_pool_fwd_kernel(const float* __restrict__ x, Geom g, long total, float* __restrict__ y) {
@@ -36,17 +22,7 @@ __global__ __launch_bounds__(PP_THREADS) void patch_pool_fwd_kernel(const float*
     const int p2 = (int)(r % a2.np); r /= a2.np;
     const int p1 = (int)(r % a1.np); r /= a1.np;
     const int p0 = (int)r;
-    const int s0 = p0 * a0.step + win_lo(a0, i0), e0 = p0 * a0.step + win_hi(a0, i0);
-    const int s1 = p1 * a1.step + win_lo(a1, i1), e1 = p1 * a1.step + win_hi(a1, i1);
-    const int s2 = p2 * a2.step + win_lo(a2, i2), e2 = p2 * a2.step + win_hi(a2, i2);
-    const float* src = x + bc * a0.n * a1.n * a2.n;
-    float acc = 0.f;
-    for (int v0 = s0; v0 < e0; ++v0)
-      for (int v1 = s1; v1 < e1; ++v1) {
-        const float* row = src + ((long)v0 * a1.n + v1) * a2.n;
-        for (int v2 = s2; v2 < e2; ++v2) acc += row[v2];
-      }
-    y[u] = acc / (float)((e0 - s0) * (e1 - s1) * (e2 - s2));
+    y[u] = window_mean(x + bc * a0.n * a1.n * a2.n, g, cell_window(g, p0, p1, p2, i0, i1, i2));
   }
 }
 
@@ -101,26 +77,6 @@ __global__ __launch_bounds__(PP_THREADS) void patch_pool_bwd_kernel(const float*
     }
     gx[u] = acc;
   }
-}
-
-// fills g; false for anything the kernels do not take.  in_elems / out_elems: the element counts of [B, C, n...] and [P, B, C, pool...].
-inline bool make_geom(int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, Geom& g, long& in_elems, long& out_elems) {
-  if ((nd != 2 && nd != 3) || B < 1 || C < 1 || patch < 2 || pool < 1 || patch > PP_MAX_SIDE || pool > PP_MAX_SIDE) return false;
-  const int n[3] = {nd == 3 ? n0 : 1, nd == 3 ? n1 : n0, nd == 3 ? n2 : n1};
-  const int step = patch / 2;
-  __int128 in = (__int128)B * C, out = in;
-  for (int d = 0; d < 3; ++d) {
-    if (nd == 2 && d == 0) { g.a[d] = Axis{1, 1, 1, 1, 1}; continue; }
-    if (n[d] < patch) return false;
-    g.a[d] = Axis{n[d], (n[d] - patch) / step + 1, patch, step, pool};
-    in *= n[d];
-    out *= (__int128)g.a[d].np * pool;
-  }
-  const __int128 lim = (__int128)1 << 40;          // far above the heads' sizes (4e6 in, 3e6 out); keeps every offset inside a long
-  if (in > lim || out > lim || (long)pool * pool * pool > 0x7fffffffL / 2 || (long)patch * patch * patch > 0x7fffffffL / 2) return false;
-  g.B = B; g.C = C;
-  in_elems = (long)in; out_elems = (long)out;
-  return true;
 }
 
 inline unsigned blocks_for(long total) {

@@ -114,8 +114,8 @@ class ISD_3d(nn.Module):
         self.K, self.m, self.Ts, self.Tt = K, m, Ts, Tt
         self.num_classes = num_classes
         self.patch_size = patch_size
-        if patch_heads not in ("torch", "gpu"):
-            raise ValueError(f"patch_heads is 'torch' or 'gpu', got {patch_heads!r}")
+        if patch_heads not in ("torch", "gpu", "fused"):
+            raise ValueError(f"patch_heads is 'torch', 'gpu' or 'fused', got {patch_heads!r}")
         self.patch_heads = patch_heads          # the route of the patch-wise output heads (stage1.patch_heads)
         self.latent_feature_size = latent_feature_size
         self.model = create_model_3d(num_classes=num_classes)

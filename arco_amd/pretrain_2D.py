@@ -8,7 +8,8 @@ the HIP kernels (arco_amd.ops), the optimizer is torch.optim.SGD(momentum=0.9, w
 (arco_sgd_momentum).  `--synthetic 1` replaces the slice loader with seeded ACDC-shaped tensors (no dataset ships with the
 reference); `--gpu_ingest 1` keeps the dataset in device memory and runs the student transform as HIP kernels, with the host
 route's random draws (dataloaders/gpu_ingest.py, dataloaders/stage1_aug.py); `--patch_heads gpu` pools the patches of the output
-heads in one HIP kernel each way (stage1.patch_heads, csrc/patch_pool.hip)."""
+heads in one HIP kernel each way (stage1.patch_heads, csrc/patch_pool.hip), `--patch_heads fused` runs their pointwise layers in the same
+kernels (csrc/patch_head.hip)."""
 import argparse
 import logging
 import os
@@ -62,10 +63,11 @@ def build_parser():
     p.add_argument('--gpu_ingest', type=int, default=0, choices=[0, 1],
                    help='1: the student transform as HIP kernels and, with --synthetic 0, the dataset in device memory, every batch one '
                         'launch (dataloaders/gpu_ingest.py, dataloaders/stage1_aug.py); 0: the host loader and the tensor-op transform')
-    p.add_argument('--patch_heads', type=str, default='torch', choices=['torch', 'gpu'],
+    p.add_argument('--patch_heads', type=str, default='torch', choices=['torch', 'gpu', 'fused'],
                    help='gpu: the patch-wise output heads pool every patch in one HIP kernel each way and run their pointwise layers once '
-                        '(csrc/patch_pool.hip, stage1.patch_heads), whatever the patch and pooling sizes; torch: the tensor-op route, patch '
-                        'by patch when the pooling windows do not tile the patch stride (the 3-D default, 20 and 8)')
+                        '(csrc/patch_pool.hip, stage1.patch_heads), whatever the patch and pooling sizes; fused: pooling and pointwise '
+                        'layers in one HIP kernel each way, parameter gradients summed in float64 (csrc/patch_head.hip); torch: the '
+                        'tensor-op route, patch by patch when the pooling windows do not tile the patch stride (the 3-D default, 20 and 8)')
     return p
 
 
@@ -214,10 +216,11 @@ def run_training(args, snapshot_path, stepper_cls, transform_student, build_load
     torch.cuda.set_device(dev)
     stepper = stepper_cls(args, dev)
     loader = None if args.synthetic else build_loader(args)
-    if getattr(args, "patch_heads", "torch") == "gpu":
+    if getattr(args, "patch_heads", "torch") in ("gpu", "fused"):
         m, step = stepper.model, max(stepper.model.patch_size // 2, 1)
         n_patches = int(np.prod([(s - m.patch_size) // step + 1 for s in args.patch_size]))
-        logging.info("patch heads on the gpu route: {} patches of size {} pooled to {}".format(n_patches, m.patch_size, args.output_pooling_size))
+        logging.info("patch heads on the {} route: {} patches of size {} pooled to {}".format(args.patch_heads, n_patches, m.patch_size,
+                                                                                             args.output_pooling_size))
     if getattr(args, "gpu_ingest", 0):
         from .dataloaders import gpu_ingest, stage1_aug
         transform_student = stage1_aug.device_transform(transform_student)

@@ -72,6 +72,110 @@ class PatchPoolFn(torch.autograd.Function):
         return gx, None, None
 
 
+FUSED_MAX_LAYERS, FUSED_MAX_WIDTH = 4, 32          # csrc/patch_head.hip PH_MAX_LAYERS, PH_MAX_WIDTH
+
+
+class PatchHeadFn(torch.autograd.Function):
+    """PatchPoolFn followed by 1 to 4 pointwise layers (kernel-1 convolutions, no non-linearity between them) as one kernel each way
+    (csrc/patch_head.hip): x [B, C, n...] -> [P * B, C_out, pool...], the stacked tensor of patch_heads(route="gpu").  params is
+    (weight, bias or None) per layer, flattened.  The pooled tensor [P, B, C, pool...] is saved; the backward computes the layers'
+    activations again from it, sums the parameter gradients in float64 and runs PatchPoolFn's backward kernel on the gradient of the
+    pooled tensor - unless x needs no gradient (the teacher's map), which skips both that kernel and the tensor."""
+
+    @staticmethod
+    def forward(ctx, x, patch, pool, *params):
+        from . import _lib as L
+        L.require_gpu(x, *params)
+        if x.dtype != torch.float32 or x.dim() not in (4, 5):
+            raise ValueError(f"PatchHeadFn: an fp32 [B, C, n...] map with 2 or 3 spatial axes, got {x.dtype} {tuple(x.shape)}")
+        n_layers = len(params) // 2
+        if len(params) % 2 or not 1 <= n_layers <= FUSED_MAX_LAYERS:
+            raise ValueError(f"PatchHeadFn: 1 to {FUSED_MAX_LAYERS} (weight, bias) pairs, got {len(params)} tensors")
+        x = x.contiguous()
+        nd, n = x.dim() - 2, tuple(x.shape[2:])
+        ws, bs, widths = [], [], [x.shape[1]]
+        for k in range(n_layers):
+            w, b = params[2 * k], params[2 * k + 1]
+            if w.dtype != torch.float32 or w.dim() != nd + 2 or w.shape[1] != widths[-1] or tuple(w.shape[2:]) != (1,) * nd:
+                raise ValueError(f"PatchHeadFn: layer {k} needs an fp32 weight [out, {widths[-1]}" + ", 1" * nd + f"], got {w.dtype} {tuple(w.shape)}")
+            if b is not None and (b.dtype != torch.float32 or tuple(b.shape) != (w.shape[0],)):
+                raise ValueError(f"PatchHeadFn: layer {k} needs an fp32 bias [{w.shape[0]}], got {b.dtype} {tuple(b.shape)}")
+            ws.append(w.detach().contiguous())
+            bs.append(None if b is None else b.detach().contiguous())
+            widths.append(w.shape[0])
+        if max(widths) > FUSED_MAX_WIDTH:
+            raise ValueError(f"PatchHeadFn: widths up to {FUSED_MAX_WIDTH}, got {widths}")
+        step = max(int(patch) // 2, 1)
+        P = 1
+        for s in n:
+            P *= max((s - patch) // step + 1, 0)          # 0: no patch fits; the entry point refuses the empty output
+        B, C = x.shape[0], x.shape[1]
+        cells = (int(pool),) * nd
+        pooled = torch.empty((P, B, C) + cells, dtype=torch.float32, device=x.device)
+        y = torch.empty((P * B, widths[-1]) + cells, dtype=torch.float32, device=x.device)
+        pad = FUSED_MAX_LAYERS - n_layers
+        ctx.geom = (nd, B, C) + n + (1,) * (3 - nd) + (int(patch), int(pool))
+        ctx.chain = (n_layers, tuple(widths[1:]) + (0,) * pad)
+        L.call("arco_patch_head_fwd", L.ptr(x), *ctx.geom, n_layers, *_chain_ptrs(ws, bs, pad), *ctx.chain[1], L.ptr(pooled), L.ptr(y))
+        ctx.has_bias = [b is not None for b in bs]
+        ctx.save_for_backward(pooled, *ws, *[b for b in bs if b is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import _lib as L
+        nd, B, C = ctx.geom[:3]
+        n_layers, widths = ctx.chain
+        pad = FUSED_MAX_LAYERS - n_layers
+        pooled, saved = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
+        ws, rest = saved[:n_layers], saved[n_layers:]
+        bs = [rest.pop(0) if hb else None for hb in ctx.has_bias]
+        gy = gy.contiguous()
+        need = ctx.needs_input_grad
+        d0 = torch.empty_like(pooled) if need[0] else None
+        n_bytes = L.query("arco_patch_head_ws_bytes", *ctx.geom, n_layers, *widths)
+        if n_bytes <= 0:
+            raise RuntimeError(f"arco_amd: arco_patch_head_ws_bytes refused {ctx.geom} {ctx.chain}")
+        slabs = torch.empty(n_bytes // 8, dtype=torch.float64, device=gy.device)
+        L.call("arco_patch_head_bwd", L.ptr(pooled), L.ptr(gy), *ctx.geom, n_layers, *_chain_ptrs(ws, bs, pad), *widths, L.ptr(d0), L.ptr(slabs))
+        grads = []
+        for k in range(n_layers):
+            grads.append(torch.empty_like(ws[k]) if need[3 + 2 * k] else None)
+            grads.append(torch.empty_like(bs[k]) if bs[k] is not None and need[4 + 2 * k] else None)
+        if any(g is not None for g in grads):
+            L.call("arco_patch_head_wgrad_finish", L.ptr(slabs), *ctx.geom, n_layers, *widths, *[L.ptr(g) for g in grads], *[None] * (2 * pad))
+        gx = None
+        if need[0]:
+            gx = torch.empty((B, C) + tuple(ctx.geom[3:3 + nd]), dtype=torch.float32, device=gy.device)
+            L.call("arco_patch_pool_bwd", L.ptr(d0), *ctx.geom, L.ptr(gx))
+        return (gx, None, None) + tuple(grads)
+
+
+def _chain_ptrs(ws, bs, pad):
+    from . import _lib as L
+    out = []
+    for w, b in zip(ws, bs):
+        out += [L.ptr(w), L.ptr(b)]
+    return out + [None] * (2 * pad)
+
+
+def _fused_params(layers, nd):
+    """The (weight, bias) pairs of the layers for PatchHeadFn; ValueError, naming the limit, for a head the fused kernels do not take."""
+    kind = nn.Conv2d if nd == 2 else nn.Conv3d
+    if not 1 <= len(layers) <= FUSED_MAX_LAYERS:
+        raise ValueError(f"patch_heads: the fused route takes 1 to {FUSED_MAX_LAYERS} pointwise layers, got {len(layers)}")
+    params = []
+    for l in layers:
+        one = (1,) * nd
+        if not (isinstance(l, kind) and tuple(l.kernel_size) == one and tuple(l.stride) == one and l.groups == 1
+                and tuple(l.padding) == (0,) * nd):
+            raise ValueError(f"patch_heads: the fused route takes kernel-1, stride-1, groups-1 {kind.__name__} layers without padding, got {l}")
+        if max(l.in_channels, l.out_channels) > FUSED_MAX_WIDTH:
+            raise ValueError(f"patch_heads: the fused route takes widths up to {FUSED_MAX_WIDTH}, got {l}")
+        params += [l.weight, l.bias]
+    return params
+
+
 def patch_heads(x, patch, head, predictor, route="torch"):
     """predictor(head(x[..., i:i+p, j:j+p(, k:k+p)])) for every patch of the p/2-stride grid, in the reference's loop
     order (first spatial axis outermost; model_2D.py:263-268, model_3D.py:355-359).  The head is adaptive average pooling
@@ -80,7 +184,10 @@ def patch_heads(x, patch, head, predictor, route="torch"):
     grid - the same values, hundreds of small launches less (700 patches per volume in 3-D); otherwise the patches are
     taken one by one like the reference.
     route="gpu": one PatchPoolFn call pools every patch, whatever the patch and pooling sizes, the pointwise layers run once on the
-    [P * B, C, pool...] tensor, and that STACKED tensor is returned (torch.cat of the list above, without the cat)."""
+    [P * B, C, pool...] tensor, and that STACKED tensor is returned (torch.cat of the list above, without the cat).
+    route="fused": the same stacked tensor from one PatchHeadFn call, pooling and pointwise layers in one kernel each way
+    (csrc/patch_head.hip); ValueError for a head it does not take (a layer that is not a kernel-1, stride-1, groups-1 convolution, more
+    than 4 layers, a width above 32, a map that is not fp32) - no fallback to another route."""
     nd = x.dim() - 2
     conv = F.conv2d if nd == 2 else F.conv3d
     proj = _unwrap(head).proj
@@ -95,8 +202,12 @@ def patch_heads(x, patch, head, predictor, route="torch"):
         for l in layers:
             g = conv(g, l.weight, l.bias)
         return g
+    if route == "fused":
+        if x.dtype != torch.float32:
+            raise ValueError(f"patch_heads: the fused route takes an fp32 map, got {x.dtype}")
+        return PatchHeadFn.apply(x, patch, pool_out, *_fused_params(layers, nd))
     if route != "torch":
-        raise ValueError(f"patch_heads: route is 'torch' or 'gpu', got {route!r}")
+        raise ValueError(f"patch_heads: route is 'torch', 'gpu' or 'fused', got {route!r}")
     if patch % pool_out == 0 and step % (patch // pool_out) == 0:
         w = patch // pool_out
         crop = tuple(slice(0, (x.shape[2 + d] // w) * w) for d in range(nd))
@@ -146,7 +257,7 @@ def isd_forward(isd, im_q, im_k=None, Ts=None, Tt=None):
     route = getattr(isd, "patch_heads", "torch")
     stu = patch_heads(outputs, isd.patch_size, isd.q_outputs_head, isd.outputs_predictor, route)
     tea = patch_heads(ema_output, isd.patch_size, isd.k_outputs_head, None, route)
-    stu = stu if torch.is_tensor(stu) else torch.cat(stu)          # route "gpu" returns the patches stacked already
+    stu = stu if torch.is_tensor(stu) else torch.cat(stu)          # the routes "gpu" and "fused" return the patches stacked already
     tea = tea if torch.is_tensor(tea) else torch.cat(tea)
     shp = tuple(stu.shape[1:])
     stu = stu.reshape(batch_size, -1, *shp).contiguous()

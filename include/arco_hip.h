@@ -749,6 +749,33 @@ int arco_blur_planes(float* data, long n_elems, long n_planes, int T, int H, int
 int arco_patch_pool_fwd(const float* x, int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, float* y, void* stream);
 int arco_patch_pool_bwd(const float* gy, int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, float* gx, void* stream);
 
+/* The patch-wise output heads as one kernel each way (pretrain_2D / pretrain_3D --patch_heads fused; csrc/patch_head.hip, arco_amd/stage1.py
+ * PatchHeadFn): the pooling above followed by `layers` (1 .. 4) pointwise layers without a non-linearity between them.  Geometry arguments as
+ * above.  Widths C = c_0, c_1 .. c_L, every one 1 .. 32; c_k of a layer behind `layers` is ignored.  w_k [c_k, c_{k-1}] fp32 row-major (a
+ * kernel-1 convolution weight), non-null for k <= layers and null behind; b_k [c_k] or null: no bias.  A POSITION is one (patch, batch,
+ * cell) triple, P * B * pool^nd of them.
+ * fwd: pooled [P,B,C,pool...] = arco_patch_pool_fwd's values, bit for bit; y [P*B,c_L,pool...]; per position, in fp32, every operation
+ *   rounded on its own: a_k[j] = b_k[j] (0.f without bias), then a_k[j] = a_k[j] + w_k[j,i] * a_{k-1}[i] for i ascending; y = a_L.
+ * bwd: gy in the layout of y.  Per position a_0 .. a_{L-1} again from pooled, d_L = gy, d_{k-1}[i] = 0.f, then d_{k-1}[i] = d_{k-1}[i] +
+ *   w_k[j,i] * d_k[j] for j ascending.  d0 [P,B,C,pool...] = d_0, or null: not wanted (arco_patch_pool_bwd takes it to the input).
+ *   The parameter gradients dw_k[j,i] = sum of (double)d_k[j] * (double)a_{k-1}[i], db_k[j] = sum of (double)d_k[j] over the positions
+ *   are accumulated in float64 into ws (arco_patch_head_ws_bytes; one slab per workgroup), without atomics and in an order that depends
+ *   on the position count and the widths alone: two runs give the same bits.
+ * wgrad_finish: the slabs of ws added in ascending order in float64, rounded once into gw_k [c_k, c_{k-1}] / gb_k [c_k] fp32; a null
+ *   pointer: that gradient is not wanted.  Same geometry, layers and widths as the bwd call that filled ws.
+ * ARCO_ERR_ARG before any launch for the pooling's refusals, layers outside 1 .. 4, a width above 32 or below 1, a null w_k of a present
+ * layer, a non-null pointer of an absent one, or a null tensor.  arco_patch_head_ws_bytes returns -1 for such arguments. */
+long arco_patch_head_ws_bytes(int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, int layers, int c1, int c2, int c3, int c4);
+int arco_patch_head_fwd(const float* x, int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, int layers,
+                        const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                        const float* w4, const float* b4, int c1, int c2, int c3, int c4, float* pooled, float* y, void* stream);
+int arco_patch_head_bwd(const float* pooled, const float* gy, int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, int layers,
+                        const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                        const float* w4, const float* b4, int c1, int c2, int c3, int c4, float* d0, double* ws, void* stream);
+int arco_patch_head_wgrad_finish(const double* ws, int nd, int B, int C, int n0, int n1, int n2, int patch, int pool, int layers,
+                                 int c1, int c2, int c3, int c4, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3,
+                                 float* gw4, float* gb4, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
