@@ -274,6 +274,12 @@ def query(name, *args):
     return getattr(load(), name)(*args)
 
 
+def h(name, t):
+    """Entry point `name`, or its `_h` form (f16 activation storage) where `t` - a tensor the call reads, or a bool - says f16."""
+    half = t if isinstance(t, bool) else t is not None and t.dtype == torch.float16
+    return name + "_h" if half else name
+
+
 def require_gpu(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:

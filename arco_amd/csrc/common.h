@@ -47,20 +47,33 @@ static inline void arco_launch(dim3 grid, dim3 block, size_t lds_bytes, size_t r
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-// four consecutive channels of an activation row as fp32, from fp32 or f16 storage (the *_h entry points: f16 activation storage)
-__device__ __forceinline__ f32x4 ld4f(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 ld4f(const _Float16* p) { return __builtin_convertvector(*reinterpret_cast<const f16x4_t*>(p), f32x4); }
-__device__ __forceinline__ void st4f(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void st4f(_Float16* p, f32x4 v) { *reinterpret_cast<f16x4_t*>(p) = __builtin_convertvector(v, f16x4_t); }
-// eight consecutive channels of an f16 row in one 16-byte access (the BN apply passes on f16 activation storage)
 typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x8 ld8f(const _Float16* p) { return __builtin_convertvector(*reinterpret_cast<const f16x8_t*>(p), f32x8); }
-__device__ __forceinline__ void st8f(_Float16* p, f32x8 v) { *reinterpret_cast<f16x8_t*>(p) = __builtin_convertvector(v, f16x8_t); }
-__device__ __forceinline__ f32x8 ld8p(const float* p) {      // eight per-channel parameters
-  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-  return f32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+template <int V> using f32v = float __attribute__((ext_vector_type(V)));
+// V consecutive channels of an activation row as fp32, from fp32 or f16 storage (the *_h entry points: f16 activation storage), in ONE
+// access of V * sizeof(T) bytes; a store rounds once.  rndv: what stv stores, as a later ldv reads it back.
+template <typename T, int V> __device__ __forceinline__ f32v<V> ldv(const T* p) {
+  typedef T tv __attribute__((ext_vector_type(V)));
+  return __builtin_convertvector(*reinterpret_cast<const tv*>(p), f32v<V>);
+}
+template <typename T, int V> __device__ __forceinline__ void stv(T* p, f32v<V> v) {
+  typedef T tv __attribute__((ext_vector_type(V)));
+  *reinterpret_cast<tv*>(p) = __builtin_convertvector(v, tv);
+}
+template <typename T, int V> __device__ __forceinline__ f32v<V> rndv(f32v<V> v) {
+  typedef T tv __attribute__((ext_vector_type(V)));
+  return __builtin_convertvector(__builtin_convertvector(v, tv), f32v<V>);
+}
+template <typename T> __device__ __forceinline__ f32x4 ld4f(const T* p) { return ldv<T, 4>(p); }
+template <typename T> __device__ __forceinline__ void st4f(T* p, f32x4 v) { stv<T, 4>(p, v); }
+// V per-channel fp32 parameters, 16 bytes at a time
+template <int V> __device__ __forceinline__ f32v<V> ldparam(const float* p) {
+  f32v<V> r;
+#pragma unroll
+  for (int e = 0; e < V; e += 4) {
+    const f32x4 q = *reinterpret_cast<const f32x4*>(p + e);
+    r[e] = q[0]; r[e + 1] = q[1]; r[e + 2] = q[2]; r[e + 3] = q[3];
+  }
+  return r;
 }
 __device__ __forceinline__ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

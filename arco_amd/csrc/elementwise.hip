@@ -3,7 +3,8 @@
 // vnetWithArgs.py:16-25), 2x2 max-pool, align_corners bilinear resize
 // (model_2D.py:43-52, unetWithArgs.py:74-75), channel-slice copies (the cat's),
 // flat-buffer SGD-Nesterov and EMA (train_arco_2d.py:248,306-308,432; model_2D.py:176-182).
-// All kernels: float4 per lane along the channel axis, grid-stride over pixels.
+// All kernels: a vector of channels per lane (four fp32; four or eight f16), grid-stride over pixels.
+#include <initializer_list>
 #include "common.h"
 #include "interp.h"
 
@@ -195,13 +196,13 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ Z
     if (mean && (C & 7) == 0 && 256 % q8 == 0 && ((ldz | lda | ldr) & 7) == 0 && al16(Z0) && al16(Aout) && al16(R)) {
       const long gt = (long)blockIdx.x * 256 + threadIdx.x, rstride = (long)gridDim.x * 256 / q8;
       const int c = (int)(gt % q8) * 8;
-      const f32x8 mu = ld8p(mean + c), is = ld8p(istd + c), ga = ld8p(gamma + c), be = ld8p(beta + c);
+      const f32x8 mu = ldparam<8>(mean + c), is = ldparam<8>(istd + c), ga = ldparam<8>(gamma + c), be = ldparam<8>(beta + c);
       for (long rb = gt / q8; rb < M; rb += 4 * rstride) {
         f32x8 z[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const long r = rb + u * rstride;
-          if (r < M) z[u] = ld8f(ds.X2 ? Z0 + d2s_src_row(r + row0, ds) * ldz + c : Z + r * ldz + c);
+          if (r < M) z[u] = ldv<T, 8>(ds.X2 ? Z0 + d2s_src_row(r + row0, ds) * ldz + c : Z + r * ldz + c);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -216,8 +217,8 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ Z
               else if (drop_mode == 2) y = drop_keep(seed, (uint64_t)(((r + row0) / P) * C + c + e), p) ? y * keep_scale : 0.f;
               o[e] = y;
             }
-            if (R) o += ld8f(R + r * ldr + c);
-            st8f(Aout + r * lda + c, o);
+            if (R) o += ldv<T, 8>(R + r * ldr + c);
+            stv<T, 8>(Aout + r * lda + c, o);
           }
         }
       }
@@ -384,14 +385,14 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(
     if (mean && (C & 7) == 0 && 256 % q8 == 0 && ((ldd | ldz | ldo) & 7) == 0 && al16(dA0) && al16(Z) && al16(dZ)) {
       const long gt = (long)blockIdx.x * 256 + threadIdx.x, rstride = (long)gridDim.x * 256 / q8;
       const int c = (int)(gt % q8) * 8;
-      const f32x8 mu = ld8p(mean + c), is = ld8p(istd + c), ga = ld8p(gamma + c), be = ld8p(beta + c);
-      const f32x8 sd = ld8p(sum_dy + c), sx = ld8p(sum_dyx + c);
+      const f32x8 mu = ldparam<8>(mean + c), is = ldparam<8>(istd + c), ga = ldparam<8>(gamma + c), be = ldparam<8>(beta + c);
+      const f32x8 sd = ldparam<8>(sum_dy + c), sx = ldparam<8>(sum_dyx + c);
       for (long rb = gt / q8; rb < M; rb += 2 * rstride) {
         f32x8 z[2], d[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const long r = rb + u * rstride;
-          if (r < M) { z[u] = ld8f(Z + r * ldz + c); d[u] = ld8f(ds.X2 ? dA0 + d2s_row(r + row0, ds) * ldd + c : dA + r * ldd + c); }
+          if (r < M) { z[u] = ldv<T, 8>(Z + r * ldz + c); d[u] = ldv<T, 8>(ds.X2 ? dA0 + d2s_row(r + row0, ds) * ldd + c : dA + r * ldd + c); }
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -407,7 +408,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(
               o[e] = gn ? is[e] * (ga[e] * dy - sd[e] * inv_count - xh * sx[e] * inv_count)
                         : ga[e] * is[e] * (dy - sd[e] * inv_count - xh * sx[e] * inv_count);
             }
-            st8f(dZ + r * ldo + c, o);
+            stv<T, 8>(dZ + r * ldo + c, o);
           }
         }
       }
@@ -469,80 +470,87 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(
   }
 }
 
-// ---- 2x2 max pool (nn.MaxPool2d(2), unetWithArgs.py:55-58), channels-last
-__global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const float* __restrict__ X, long ldx, int NB, int H, int W,
-                                                          int C, float* __restrict__ Y, long ldy) {
-  const int q4 = C / 4, Ho = H / 2, Wo = W / 2;
-  const long tot = (long)NB * Ho * Wo * q4;
+// ---- 2x2 max pool (nn.MaxPool2d(2), unetWithArgs.py:55-58) and align_corners bilinear resize, channels-last.  ONE kernel per
+// operator for both storage types: T = float / _Float16 in HBM, V channels per lane (fp32: 4, f16: 8 - 16-byte accesses either way),
+// fp32 arithmetic, one rounding per stored value - the f16 form equals the fp32 form on the same values, rounded once.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const T* __restrict__ X, long ldx, int NB, int H, int W, int C,
+                                                          T* __restrict__ Y, long ldy) {
+  const int qv = C / V, Ho = H / 2, Wo = W / 2;
+  const long tot = (long)NB * Ho * Wo * qv;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tot; i += (long)gridDim.x * 256) {
-    const int c = (int)(i % q4) * 4; long r = i / q4;
+    const int c = (int)(i % qv) * V; long r = i / qv;
     const int xo = r % Wo; r /= Wo; const int yo = r % Ho; const long n = r / Ho;
-    const float* b = X + (((n * H) + 2 * yo) * W + 2 * xo) * ldx + c;
-    const f32x4 v00 = *reinterpret_cast<const f32x4*>(b), v01 = *reinterpret_cast<const f32x4*>(b + ldx);
-    const f32x4 v10 = *reinterpret_cast<const f32x4*>(b + (long)W * ldx), v11 = *reinterpret_cast<const f32x4*>(b + (long)W * ldx + ldx);
-    f32x4 o;
+    const T* b = X + (((n * H) + 2 * yo) * W + 2 * xo) * ldx + c;
+    const f32v<V> v00 = ldv<T, V>(b), v01 = ldv<T, V>(b + ldx), v10 = ldv<T, V>(b + (long)W * ldx), v11 = ldv<T, V>(b + (long)W * ldx + ldx);
+    f32v<V> o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = fmaxf(fmaxf(v00[e], v01[e]), fmaxf(v10[e], v11[e]));
-    *reinterpret_cast<f32x4*>(Y + (((n * Ho) + yo) * Wo + xo) * ldy + c) = o;
+    for (int e = 0; e < V; ++e) o[e] = fmaxf(fmaxf(v00[e], v01[e]), fmaxf(v10[e], v11[e]));
+    stv<T, V>(Y + (((n * Ho) + yo) * Wo + xo) * ldy + c, o);
   }
 }
 // BN apply + LeakyReLU of a block's last stage AND the 2x2 max-pool of the result in one pass (the ConvBlock output feeds
 // the next DownBlock's nn.MaxPool2d and, unpooled, the decoder's skip: unetWithArgs.py:55-58,109-116): a thread owns a
-// 2x2 pixel window x 4 channels - four Z loads, four A stores, one pooled store; the separate pooling pass re-read A.
-// Same arithmetic per element as bn_act_fwd_kernel (no dropout on this stage) / maxpool2_fwd_kernel.
-__global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const float* __restrict__ Z, long ldz, int NB, int H, int W, int C,
+// 2x2 pixel window x V channels - four Z loads, four A stores, one pooled store; the separate pooling pass re-read A.
+// Same arithmetic per element as bn_act_fwd_kernel (no dropout on this stage), and the pooled value is the maximum of the four
+// STORED values in maxpool2_fwd_kernel's order (the pooling reads what was stored): both outputs equal, bit for bit,
+// arco_bn_act_fwd(_h) followed by arco_maxpool2_fwd(_h).  A may be the leading channels of a wider buffer (lda > C: concat room).
+// f16 also runs with V = 4 (8-byte accesses), for rows that are not whole 16-byte pieces.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void bn_act_pool_fwd_kernel(const T* __restrict__ Z, long ldz, int NB, int H, int W, int C,
                                                              const float* __restrict__ mean, const float* __restrict__ istd,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             float slope, float* __restrict__ Aout, long lda,
-                                                             float* __restrict__ Pout, long ldp, int img_per_group) {
-  const int q4 = C / 4, Ho = H / 2, Wo = W / 2;
-  const long tot = (long)NB * Ho * Wo * q4;
+                                                             float slope, T* __restrict__ Aout, long lda,
+                                                             T* __restrict__ Pout, long ldp, int img_per_group) {
+  const int qv = C / V, Ho = H / 2, Wo = W / 2;
+  const long tot = (long)NB * Ho * Wo * qv;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tot; i += (long)gridDim.x * 256) {
-    const int c = (int)(i % q4) * 4; long r = i / q4;
+    const int c = (int)(i % qv) * V; long r = i / qv;
     const int xo = r % Wo; r /= Wo; const int yo = r % Ho; const long n = r / Ho;
-    const int g = (int)(n / img_per_group);
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + (long)g * C + c), is = *reinterpret_cast<const f32x4*>(istd + (long)g * C + c);
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c), be = *reinterpret_cast<const f32x4*>(beta + c);
+    const long g = n / img_per_group;
+    const f32v<V> mu = ldparam<V>(mean + g * C + c), is = ldparam<V>(istd + g * C + c), ga = ldparam<V>(gamma + c), be = ldparam<V>(beta + c);
     const long row = ((n * H) + 2 * yo) * W + 2 * xo;
     const long rows[4] = {row, row + 1, row + W, row + W + 1};
-    f32x4 z[4];
+    f32v<V> z[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) z[u] = *reinterpret_cast<const f32x4*>(Z + rows[u] * ldz + c);
-    f32x4 o[4];
+    for (int u = 0; u < 4; ++u) z[u] = ldv<T, V>(Z + rows[u] * ldz + c);
+    f32v<V> o[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
+      for (int e = 0; e < V; ++e) {
         float y = (z[u][e] - mu[e]) * is[e] * ga[e] + be[e];
         o[u][e] = y >= 0.f ? y : y * slope;
       }
-      *reinterpret_cast<f32x4*>(Aout + rows[u] * lda + c) = o[u];
+      stv<T, V>(Aout + rows[u] * lda + c, o[u]);
+      o[u] = rndv<T, V>(o[u]);
     }
-    f32x4 m;
+    f32v<V> m;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) m[e] = fmaxf(fmaxf(o[0][e], o[1][e]), fmaxf(o[2][e], o[3][e]));
-    *reinterpret_cast<f32x4*>(Pout + (((n * Ho) + yo) * Wo + xo) * ldp + c) = m;
+    for (int e = 0; e < V; ++e) m[e] = fmaxf(fmaxf(o[0][e], o[1][e]), fmaxf(o[2][e], o[3][e]));
+    stv<T, V>(Pout + (((n * Ho) + yo) * Wo + xo) * ldp + c, m);
   }
 }
-// gradient goes to the first maximum in window scan order (torch's saved argmax)
-__global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restrict__ X, long ldx, int NB, int H, int W,
-                                                          int C, const float* __restrict__ dY, long ldy,
-                                                          float* __restrict__ dX, long ldo,
-                                                          const float* __restrict__ add, long lda) {
-  const int q4 = C / 4, Ho = H / 2, Wo = W / 2;
-  const long tot = (long)NB * Ho * Wo * q4;
+// gradient goes to the first maximum in window scan order (torch's saved argmax); a routed value needs no rounding, the sum with
+// `add` is formed in fp32 and rounded once
+template <typename T, int V>
+__global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const T* __restrict__ X, long ldx, int NB, int H, int W, int C,
+                                                          const T* __restrict__ dY, long ldy, T* __restrict__ dX, long ldo,
+                                                          const T* __restrict__ add, long lda) {
+  const int qv = C / V, Ho = H / 2, Wo = W / 2;
+  const long tot = (long)NB * Ho * Wo * qv;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tot; i += (long)gridDim.x * 256) {
-    const int c = (int)(i % q4) * 4; long r = i / q4;
+    const int c = (int)(i % qv) * V; long r = i / qv;
     const int xo = r % Wo; r /= Wo; const int yo = r % Ho; const long n = r / Ho;
     const long p00 = ((n * H) + 2 * yo) * W + 2 * xo;
     const long off[4] = {p00, p00 + 1, p00 + W, p00 + W + 1};
-    f32x4 v[4];
+    f32v<V> v[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const f32x4*>(X + off[k] * ldx + c);
-    const f32x4 g = *reinterpret_cast<const f32x4*>(dY + (((n * Ho) + yo) * Wo + xo) * ldy + c);
-    f32x4 o[4];
+    for (int k = 0; k < 4; ++k) v[k] = ldv<T, V>(X + off[k] * ldx + c);
+    const f32v<V> g = ldv<T, V>(dY + (((n * Ho) + yo) * Wo + xo) * ldy + c);
+    f32v<V> o[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < V; ++e) {
       int best = 0; float bv = v[0][e];
 #pragma unroll
       for (int k = 1; k < 4; ++k) if (v[k][e] > bv) { bv = v[k][e]; best = k; }
@@ -551,74 +559,72 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restri
     }
     if (add) {           // + the gradient of the other consumer of x (the decoder's skip connection): no separate add kernel
 #pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] += *reinterpret_cast<const f32x4*>(add + off[k] * lda + c);
+      for (int k = 0; k < 4; ++k) o[k] += ldv<T, V>(add + off[k] * lda + c);
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(dX + off[k] * ldo + c) = o[k];
+    for (int k = 0; k < 4; ++k) stv<T, V>(dX + off[k] * ldo + c, o[k]);
   }
 }
 
-// ---- bilinear resize, align_corners=True (torch upsample_bilinear2d index math in fp32)
-// (ac_src: igemm_args.h)
-__global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restrict__ X, long ldx, int NB, int Hi, int Wi,
-                                                          int C, int Ho, int Wo, float* __restrict__ Y, long ldy) {
-  const int q4 = C / 4;
+// ---- bilinear resize, align_corners=True (torch upsample_bilinear2d index math in fp32; ac_src, bl_blend1: interp.h)
+template <typename T, int V>
+__global__ __launch_bounds__(256) void bilinear_fwd_kernel(const T* __restrict__ X, long ldx, int NB, int Hi, int Wi, int C,
+                                                          int Ho, int Wo, T* __restrict__ Y, long ldy) {
+  const int qv = C / V;
   const float sh = Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f, sw = Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f;
-  const long tot = (long)NB * Ho * Wo * q4;
+  const long tot = (long)NB * Ho * Wo * qv;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tot; i += (long)gridDim.x * 256) {
-    const int c = (int)(i % q4) * 4; long r = i / q4;
+    const int c = (int)(i % qv) * V; long r = i / qv;
     const int xo = r % Wo; r /= Wo; const int yo = r % Ho; const long n = r / Ho;
     int y0, y1, x0, x1; float ly, lx;
     ac_src(yo, sh, Hi, y0, y1, ly); ac_src(xo, sw, Wi, x0, x1, lx);
     const float hy = 1.f - ly, hx = 1.f - lx;
-    const float* b = X + (n * Hi) * (long)Wi * ldx + c;
-    const f32x4 v00 = *reinterpret_cast<const f32x4*>(b + ((long)y0 * Wi + x0) * ldx);
-    const f32x4 v01 = *reinterpret_cast<const f32x4*>(b + ((long)y0 * Wi + x1) * ldx);
-    const f32x4 v10 = *reinterpret_cast<const f32x4*>(b + ((long)y1 * Wi + x0) * ldx);
-    const f32x4 v11 = *reinterpret_cast<const f32x4*>(b + ((long)y1 * Wi + x1) * ldx);
-    f32x4 o;
+    const T* b = X + (n * Hi) * (long)Wi * ldx + c;
+    const f32v<V> v00 = ldv<T, V>(b + ((long)y0 * Wi + x0) * ldx), v01 = ldv<T, V>(b + ((long)y0 * Wi + x1) * ldx);
+    const f32v<V> v10 = ldv<T, V>(b + ((long)y1 * Wi + x0) * ldx), v11 = ldv<T, V>(b + ((long)y1 * Wi + x1) * ldx);
+    f32v<V> o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = bl_blend1(v00[e], v01[e], v10[e], v11[e], hx, lx, hy, ly);
-    *reinterpret_cast<f32x4*>(Y + (((n * Ho) + yo) * Wo + xo) * ldy + c) = o;
+    for (int e = 0; e < V; ++e) o[e] = bl_blend1(v00[e], v01[e], v10[e], v11[e], hx, lx, hy, ly);
+    stv<T, V>(Y + (((n * Ho) + yo) * Wo + xo) * ldy + c, o);
   }
 }
 // adjoint as a gather (no atomics): input pixel (yi, xi) collects from the output pixels that
 // reference it; candidate output ranges are bounded by the scale and verified with ac_src.
-__global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restrict__ dY, long ldy, int NB, int Hi, int Wi,
-                                                          int C, int Ho, int Wo, float* __restrict__ dX, long ldx,
-                                                          int accumulate) {
-  const int q4 = C / 4;
+template <typename T, int V>
+__global__ __launch_bounds__(256) void bilinear_bwd_kernel(const T* __restrict__ dY, long ldy, int NB, int Hi, int Wi, int C,
+                                                          int Ho, int Wo, T* __restrict__ dX, long ldx, int accumulate) {
+  const int qv = C / V;
   const float sh = Ho > 1 ? (float)(Hi - 1) / (float)(Ho - 1) : 0.f, sw = Wo > 1 ? (float)(Wi - 1) / (float)(Wo - 1) : 0.f;
   const float ish = sh > 0.f ? 1.f / sh : 0.f, isw = sw > 0.f ? 1.f / sw : 0.f;
-  const long tot = (long)NB * Hi * Wi * q4;
+  const long tot = (long)NB * Hi * Wi * qv;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tot; i += (long)gridDim.x * 256) {
-    const int c = (int)(i % q4) * 4; long r = i / q4;
+    const int c = (int)(i % qv) * V; long r = i / qv;
     const int xi = r % Wi; r /= Wi; const int yi = r % Hi; const long n = r / Hi;
     int ya = sh > 0.f ? (int)floorf((float)(yi - 1) * ish) - 1 : 0, yb = sh > 0.f ? (int)ceilf((float)(yi + 1) * ish) + 1 : Ho - 1;
     int xa = sw > 0.f ? (int)floorf((float)(xi - 1) * isw) - 1 : 0, xb = sw > 0.f ? (int)ceilf((float)(xi + 1) * isw) + 1 : Wo - 1;
     ya = max(ya, 0); yb = min(yb, Ho - 1); xa = max(xa, 0); xb = min(xb, Wo - 1);
-    f32x4 acc = {0, 0, 0, 0};
+    f32v<V> acc = 0.f;
     for (int yo = ya; yo <= yb; ++yo) {
       int y0, y1; float ly; ac_src(yo, sh, Hi, y0, y1, ly);
       float wy = 0.f;
       if (y0 == yi) wy += 1.f - ly;
       if (y1 == yi) wy += ly;
-      if (wy == 0.f && !(y0 == yi || y1 == yi)) continue;
+      if (!(y0 == yi || y1 == yi)) continue;
       for (int xo = xa; xo <= xb; ++xo) {
         int x0, x1; float lx; ac_src(xo, sw, Wi, x0, x1, lx);
         float wx = 0.f;
         if (x0 == xi) wx += 1.f - lx;
         if (x1 == xi) wx += lx;
         if (!(x0 == xi || x1 == xi)) continue;
-        const f32x4 g = *reinterpret_cast<const f32x4*>(dY + (((n * Ho) + yo) * Wo + xo) * ldy + c);
+        const f32v<V> g = ldv<T, V>(dY + (((n * Ho) + yo) * Wo + xo) * ldy + c);
         const float w = wy * wx;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += w * g[e];
+        for (int e = 0; e < V; ++e) acc[e] += w * g[e];
       }
     }
-    float* dst = dX + (((n * Hi) + yi) * Wi + xi) * ldx + c;
-    if (accumulate) { const f32x4 old = *reinterpret_cast<const f32x4*>(dst); acc += old; }
-    *reinterpret_cast<f32x4*>(dst) = acc;
+    T* dst = dX + (((n * Hi) + yi) * Wi + xi) * ldx + c;
+    if (accumulate) acc += ldv<T, V>(dst);
+    stv<T, V>(dst, acc);
   }
 }
 
@@ -1341,51 +1347,124 @@ int arco_gn_act_bwd(const float* dA, long ldd, const float* Z, long ldz, long M,
                          dZ, ldo, nullptr, N, cpg, stream);
 }
 
-int arco_maxpool2_fwd(const float* X, long ldx, int NB, int H, int W, int C, float* Y, long ldy, void* stream) {
-  ARCO_CHECK_ARG((C & 3) == 0 && (H & 1) == 0 && (W & 1) == 0);
-  hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(ew_grid((long)NB * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0,
+// ---- pooling and resize: every plain / _h pair is two argument checks in front of one launcher.  The f16 entries take whole 16-byte
+// lanes only (C and every row stride a multiple of 8, every pointer 16-byte aligned; arco_bn_act_pool_fwd_h falls back to 8-byte lanes)
+extern "C++" {
+static bool arco_h8_ok(std::initializer_list<const void*> ptrs, std::initializer_list<long> lds) {
+  for (const void* p : ptrs) if (!p || !ew_al16(p)) return false;
+  for (long l : lds) if ((l & 7) != 0) return false;
+  return true;
+}
+static inline const _Float16* as_h(const void* p) { return reinterpret_cast<const _Float16*>(p); }
+static inline _Float16* as_h(void* p) { return reinterpret_cast<_Float16*>(p); }
+
+template <typename T, int V>
+static int maxpool2_fwd_impl(const T* X, long ldx, int NB, int H, int W, int C, T* Y, long ldy, void* stream) {
+  hipLaunchKernelGGL((maxpool2_fwd_kernel<T, V>), dim3(ew_grid((long)NB * (H / 2) * (W / 2) * (C / V))), dim3(256), 0,
                      as_stream(stream), X, ldx, NB, H, W, C, Y, ldy);
   return arco_launch_status();
 }
+template <typename T, int V>
+static int bn_act_pool_fwd_impl(const T* Z, long ldz, int NB, int H, int W, int C, const float* mean, const float* istd,
+                                const float* gamma, const float* beta, float slope, T* A, long lda, T* P, long ldp, int groups,
+                                void* stream) {
+  hipLaunchKernelGGL((bn_act_pool_fwd_kernel<T, V>), dim3(ew_grid((long)NB * (H / 2) * (W / 2) * (C / V))), dim3(256), 0,
+                     as_stream(stream), Z, ldz, NB, H, W, C, mean, istd, gamma, beta, slope, A, lda, P, ldp, NB / groups);
+  return arco_launch_status();
+}
+// add == nullptr: no skip gradient
+template <typename T, int V>
+static int maxpool2_bwd_impl(const T* X, long ldx, int NB, int H, int W, int C, const T* dY, long ldy, const T* add, long ld_add,
+                             T* dX, long ldo, void* stream) {
+  hipLaunchKernelGGL((maxpool2_bwd_kernel<T, V>), dim3(ew_grid((long)NB * (H / 2) * (W / 2) * (C / V))), dim3(256), 0,
+                     as_stream(stream), X, ldx, NB, H, W, C, dY, ldy, dX, ldo, add, ld_add);
+  return arco_launch_status();
+}
+template <typename T, int V>
+static int bilinear_fwd_impl(const T* X, long ldx, int NB, int Hi, int Wi, int C, int Ho, int Wo, T* Y, long ldy, void* stream) {
+  hipLaunchKernelGGL((bilinear_fwd_kernel<T, V>), dim3(ew_grid((long)NB * Ho * Wo * (C / V))), dim3(256), 0, as_stream(stream),
+                     X, ldx, NB, Hi, Wi, C, Ho, Wo, Y, ldy);
+  return arco_launch_status();
+}
+template <typename T, int V>
+static int bilinear_bwd_impl(const T* dY, long ldy, int NB, int Hi, int Wi, int C, int Ho, int Wo, T* dX, long ldx, int accumulate,
+                             void* stream) {
+  hipLaunchKernelGGL((bilinear_bwd_kernel<T, V>), dim3(ew_grid((long)NB * Hi * Wi * (C / V))), dim3(256), 0, as_stream(stream),
+                     dY, ldy, NB, Hi, Wi, C, Ho, Wo, dX, ldx, accumulate);
+  return arco_launch_status();
+}
+}  // extern "C++"
+
+int arco_maxpool2_fwd(const float* X, long ldx, int NB, int H, int W, int C, float* Y, long ldy, void* stream) {
+  ARCO_CHECK_ARG((C & 3) == 0 && (H & 1) == 0 && (W & 1) == 0);
+  return maxpool2_fwd_impl<float, 4>(X, ldx, NB, H, W, C, Y, ldy, stream);
+}
+int arco_maxpool2_fwd_h(const void* X, long ldx, int NB, int H, int W, int C, void* Y, long ldy, void* stream) {
+  ARCO_CHECK_ARG(C > 0 && (C & 7) == 0 && (H & 1) == 0 && (W & 1) == 0 && NB > 0 && arco_h8_ok({X, Y}, {ldx, ldy}));
+  return maxpool2_fwd_impl<_Float16, 8>(as_h(X), ldx, NB, H, W, C, as_h(Y), ldy, stream);
+}
+// A [pix][0..C) = lrelu(BN(Z)) and P = maxpool2(A) in one pass; mean / istd [groups][C], gamma / beta [C], fp32
 int arco_bn_act_pool_fwd(const float* Z, long ldz, int NB, int H, int W, int C, const float* mean, const float* istd,
                          const float* gamma, const float* beta, float slope, float* A, long lda, float* P, long ldp,
                          int groups, void* stream) {
   if (groups < 1) groups = 1;
   ARCO_CHECK_ARG(Z && mean && istd && gamma && beta && A && P && C > 0 && (C & 3) == 0 && (ldz & 3) == 0 && (lda & 3) == 0 &&
                  (ldp & 3) == 0 && (H & 1) == 0 && (W & 1) == 0 && NB % groups == 0);
-  hipLaunchKernelGGL(bn_act_pool_fwd_kernel, dim3(ew_grid((long)NB * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0,
-                     as_stream(stream), Z, ldz, NB, H, W, C, mean, istd, gamma, beta, slope, A, lda, P, ldp, NB / groups);
-  return arco_launch_status();
+  return bn_act_pool_fwd_impl<float, 4>(Z, ldz, NB, H, W, C, mean, istd, gamma, beta, slope, A, lda, P, ldp, groups, stream);
+}
+// f16 Z, A, P: 16-byte lanes where every pointer and row stride allows them, else 8-byte lanes (C and the strides multiples of 4)
+int arco_bn_act_pool_fwd_h(const void* Z, long ldz, int NB, int H, int W, int C, const float* mean, const float* istd,
+                           const float* gamma, const float* beta, float slope, void* A, long lda, void* P, long ldp, int groups,
+                           void* stream) {
+  if (groups < 1) groups = 1;
+  ARCO_CHECK_ARG(Z && mean && istd && gamma && beta && A && P && NB > 0 && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && (H & 1) == 0 &&
+                 (W & 1) == 0 && NB % groups == 0 && ldz >= C && lda >= C && ldp >= C && ((ldz | lda | ldp) & 3) == 0);
+  for (const void* p : {Z, (const void*)A, (const void*)P}) ARCO_CHECK_ARG(ew_al8(p));
+  for (const void* p : {(const void*)mean, (const void*)istd, (const void*)gamma, (const void*)beta}) ARCO_CHECK_ARG(ew_al16(p));
+  if ((C & 7) == 0 && arco_h8_ok({Z, A, P}, {ldz, lda, ldp}))
+    return bn_act_pool_fwd_impl<_Float16, 8>(as_h(Z), ldz, NB, H, W, C, mean, istd, gamma, beta, slope, as_h(A), lda, as_h(P), ldp, groups, stream);
+  return bn_act_pool_fwd_impl<_Float16, 4>(as_h(Z), ldz, NB, H, W, C, mean, istd, gamma, beta, slope, as_h(A), lda, as_h(P), ldp, groups, stream);
 }
 int arco_maxpool2_bwd(const float* X, long ldx, int NB, int H, int W, int C, const float* dY, long ldy, float* dX,
                       long ldo, void* stream) {
   ARCO_CHECK_ARG((C & 3) == 0 && (H & 1) == 0 && (W & 1) == 0);
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid((long)NB * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0,
-                     as_stream(stream), X, ldx, NB, H, W, C, dY, ldy, dX, ldo, (const float*)nullptr, 0l);
-  return arco_launch_status();
+  return maxpool2_bwd_impl<float, 4>(X, ldx, NB, H, W, C, dY, ldy, nullptr, 0, dX, ldo, stream);
+}
+int arco_maxpool2_bwd_h(const void* X, long ldx, int NB, int H, int W, int C, const void* dY, long ldy, void* dX, long ldo,
+                        void* stream) {
+  ARCO_CHECK_ARG(C > 0 && (C & 7) == 0 && (H & 1) == 0 && (W & 1) == 0 && NB > 0 && arco_h8_ok({X, dY, dX}, {ldx, ldy, ldo}));
+  return maxpool2_bwd_impl<_Float16, 8>(as_h(X), ldx, NB, H, W, C, as_h(dY), ldy, nullptr, 0, as_h(dX), ldo, stream);
 }
 // dX = maxpool2_bwd(dY) + add  (add: the gradient x receives from its other consumer, e.g. the U-Net skip connection)
 int arco_maxpool2_bwd_add(const float* X, long ldx, int NB, int H, int W, int C, const float* dY, long ldy, const float* add,
                           long ld_add, float* dX, long ldo, void* stream) {
   ARCO_CHECK_ARG((C & 3) == 0 && (H & 1) == 0 && (W & 1) == 0 && add && (ld_add & 3) == 0);
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(ew_grid((long)NB * (H / 2) * (W / 2) * (C / 4))), dim3(256), 0,
-                     as_stream(stream), X, ldx, NB, H, W, C, dY, ldy, dX, ldo, add, ld_add);
-  return arco_launch_status();
+  return maxpool2_bwd_impl<float, 4>(X, ldx, NB, H, W, C, dY, ldy, add, ld_add, dX, ldo, stream);
+}
+int arco_maxpool2_bwd_add_h(const void* X, long ldx, int NB, int H, int W, int C, const void* dY, long ldy, const void* add,
+                            long ld_add, void* dX, long ldo, void* stream) {
+  ARCO_CHECK_ARG(C > 0 && (C & 7) == 0 && (H & 1) == 0 && (W & 1) == 0 && NB > 0 &&
+                 arco_h8_ok({X, dY, add, dX}, {ldx, ldy, ld_add, ldo}));
+  return maxpool2_bwd_impl<_Float16, 8>(as_h(X), ldx, NB, H, W, C, as_h(dY), ldy, as_h(add), ld_add, as_h(dX), ldo, stream);
 }
 
 int arco_bilinear_fwd(const float* X, long ldx, int NB, int Hi, int Wi, int C, int Ho, int Wo, float* Y, long ldy,
                       void* stream) {
   ARCO_CHECK_ARG((C & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0);
-  hipLaunchKernelGGL(bilinear_fwd_kernel, dim3(ew_grid((long)NB * Ho * Wo * (C / 4))), dim3(256), 0, as_stream(stream),
-                     X, ldx, NB, Hi, Wi, C, Ho, Wo, Y, ldy);
-  return arco_launch_status();
+  return bilinear_fwd_impl<float, 4>(X, ldx, NB, Hi, Wi, C, Ho, Wo, Y, ldy, stream);
+}
+int arco_bilinear_fwd_h(const void* X, long ldx, int NB, int Hi, int Wi, int C, int Ho, int Wo, void* Y, long ldy, void* stream) {
+  ARCO_CHECK_ARG(C > 0 && (C & 7) == 0 && NB > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && arco_h8_ok({X, Y}, {ldx, ldy}));
+  return bilinear_fwd_impl<_Float16, 8>(as_h(X), ldx, NB, Hi, Wi, C, Ho, Wo, as_h(Y), ldy, stream);
 }
 int arco_bilinear_bwd(const float* dY, long ldy, int NB, int Hi, int Wi, int C, int Ho, int Wo, float* dX, long ldx,
                       int accumulate, void* stream) {
   ARCO_CHECK_ARG((C & 3) == 0 && (ldx & 3) == 0 && (ldy & 3) == 0);
-  hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(ew_grid((long)NB * Hi * Wi * (C / 4))), dim3(256), 0, as_stream(stream),
-                     dY, ldy, NB, Hi, Wi, C, Ho, Wo, dX, ldx, accumulate);
-  return arco_launch_status();
+  return bilinear_bwd_impl<float, 4>(dY, ldy, NB, Hi, Wi, C, Ho, Wo, dX, ldx, accumulate, stream);
+}
+int arco_bilinear_bwd_h(const void* dY, long ldy, int NB, int Hi, int Wi, int C, int Ho, int Wo, void* dX, long ldx, void* stream) {
+  ARCO_CHECK_ARG(C > 0 && (C & 7) == 0 && NB > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && arco_h8_ok({dY, dX}, {ldy, ldx}));
+  return bilinear_bwd_impl<_Float16, 8>(as_h(dY), ldy, NB, Hi, Wi, C, Ho, Wo, as_h(dX), ldx, 0, stream);
 }
 
 int arco_gather_upcat_rows(const float* lo, long ldlo, int Clo, int Hi, int Wi, const float* hi, long ldhi, int Chi,

@@ -728,7 +728,10 @@ static int dispatch_halo(const IgemmArgs& a, hipStream_t st, int* q) {
 // and spends 16x the work) - this is a streaming kernel: 2 MB in, 33.5 MB out at 8x256x256.  A lane owns 4
 // output channels of one pixel (16-byte coalesced stores), the 6x18 input halo and the weights sit in LDS,
 // workgroups are persistent so the BN partials stay <= 1024 slabs.
+// TOut = _Float16: this layer opens the f16 region (f16 activation storage) - a.C is an f16 tensor, a value is rounded once on the
+// 8-byte store and the BatchNorm partials are sums over the ROUNDED values.
 // ---------------------------------------------------------------------------
+template <typename TOut>
 __global__ __launch_bounds__(256) void conv3x3_image_kernel(IgemmArgs a) {
   constexpr int TH = 16, TW = 16, HW_ = TW + 2, NP = (TH + 2) * HW_;
   __shared__ float Xs[4][NP];            // [k][halo pixel]
@@ -774,7 +777,13 @@ __global__ __launch_bounds__(256) void conv3x3_image_kernel(IgemmArgs a) {
       const int gy = ty * TH + py, gx = tx * TW + px;
       if (gy < a.H && gx < a.W && 4 * qd < a.N) {
         const long pix = ((long)nb * a.H + gy) * a.W + gx;
-        *reinterpret_cast<f32x4*>(a.C + pix * a.ldc + 4 * qd) = acc;
+        if constexpr (sizeof(TOut) == 2) {
+          const f16x4 hv = to_f16x4(acc);
+          *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(a.C) + pix * a.ldc + 4 * qd) = hv;
+          acc = __builtin_convertvector(hv, f32x4);
+        } else {
+          *reinterpret_cast<f32x4*>(a.C + pix * a.ldc + 4 * qd) = acc;
+        }
         s1 += acc; s2 += acc * acc;
       }
     }
@@ -891,18 +900,45 @@ static int launch_image_conv3d(const IgemmArgs& a, hipStream_t st, int* q) {
 static bool image_conv_eligible(const IgemmArgs& a) {
   return a.K <= 4 && a.Npad == 16 && (a.N & 3) == 0 && (a.ldc & 3) == 0 && a.R == nullptr;
 }
+// workgroups of conv3x3_image_kernel (= BatchNorm partial slabs per channel): whole 16 x 16 tiles per BN group, at most 1024 in all
+static long image_conv_blocks(int NB, int H, int W, int n_grp) {
+  const long n_tiles = (long)NB * ((H + 15) / 16) * ((W + 15) / 16);
+  long bpg = 1024 / n_grp; if (bpg > n_tiles / n_grp) bpg = n_tiles / n_grp; if (bpg < 1) bpg = 1;
+  return bpg * n_grp;
+}
 static int launch_image_conv(const IgemmArgs& a, hipStream_t st, int* q) {
-  const long n_tiles = (long)a.NB * ((a.H + 15) / 16) * ((a.W + 15) / 16);
   const int n_grp = a.stat_groups > 1 ? a.stat_groups : 1;
   if (a.NB % n_grp != 0) return ARCO_ERR_ARG;
-  long bpg = 1024 / n_grp; if (bpg > n_tiles / n_grp) bpg = n_tiles / n_grp; if (bpg < 1) bpg = 1;
-  const long blocks = bpg * n_grp;
+  const long blocks = image_conv_blocks(a.NB, a.H, a.W, n_grp);
   if (q) { q[0] = (int)blocks; q[1] = 9 * 1000000 + 800000 + a.K * 1000 + 16; q[2] = 10; return ARCO_OK; }
   IgemmArgs b = a; b.n_mblocks = (int)blocks; b.n_nblocks = 1;
   arco_note_route(9 * 1000000 + 800000 + a.K * 1000 + 16);
-  hipLaunchKernelGGL(conv3x3_image_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b);
+  hipLaunchKernelGGL(conv3x3_image_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, b);
   return arco_launch_status();
 }
+extern "C" {
+// number of BatchNorm partial slabs per channel that arco_conv3x3_image_fwd_h writes (= its workgroups)
+int arco_conv3x3_image_mblocks_h(int NB, int H, int W, int stat_groups) {
+  const int n_grp = stat_groups > 1 ? stat_groups : 1;
+  if (NB <= 0 || H <= 0 || W <= 0 || NB % n_grp != 0) return ARCO_ERR_ARG;
+  return (int)image_conv_blocks(NB, H, W, n_grp);
+}
+// out (f16) [pix][0..N) = conv3x3(in (fp32 image, K <= 4 channels); Wp: the fp32 forward pack [9][16][16]) + bias; N <= 16
+int arco_conv3x3_image_fwd_h(const float* in, long ld_in, int K, const float* Wp, int N, void* out, long ld_out, const float* bias,
+                             float* stat_sum, float* stat_sq, int NB, int H, int W, int stat_groups, void* stream) {
+  const int n_grp = stat_groups > 1 ? stat_groups : 1;
+  ARCO_CHECK_ARG(in && Wp && out && K >= 1 && K <= 4 && N >= 4 && N <= 16 && (N & 3) == 0 && (ld_out & 3) == 0 && ld_in >= K &&
+                 NB > 0 && H > 0 && W > 0 && NB % n_grp == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0 &&
+                 (stat_sum == nullptr) == (stat_sq == nullptr));
+  IgemmArgs a = {};
+  a.A = in; a.lda = ld_in; a.Wp = Wp; a.Npad = 16; a.Kpad = 16; a.N = N; a.K = K;
+  a.C = reinterpret_cast<float*>(out); a.ldc = ld_out; a.bias = bias; a.stat_sum = stat_sum; a.stat_sq = stat_sq;
+  a.NB = NB; a.H = H; a.W = W; a.stat_groups = n_grp;
+  a.n_mblocks = (int)image_conv_blocks(NB, H, W, n_grp);
+  hipLaunchKernelGGL(conv3x3_image_kernel<_Float16>, dim3((unsigned)a.n_mblocks), dim3(256), 0, as_stream(stream), a);
+  return arco_launch_status();
+}
+}  // extern "C"
 // ---------------------------------------------------------------------------------------------------------------------------
 // Streaming 1x1(x1) convolutions with a handful of channels on one side (round 6).  The V-Net's out_conv (16 -> classes,
 // vnetWithArgs.py:182) and its data gradient (classes -> 16) run over the FULL-resolution map: 128 MB (LA) per launch for

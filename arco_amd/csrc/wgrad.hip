@@ -1057,6 +1057,60 @@ static int conv3d_wgrad_impl(const float* dZ, long ld_dz, int Cout, const float*
   return arco_launch_status();
 }
 
+// The first 2-D layer under f16 activation storage: dW[co][ci][tap] = sum_pix dZ[pix][co] X[pix + tap][ci] from the f16 dZ (16
+// channels) and the fp32 IMAGE (1 - 4 channels).  A thread owns one (co, tap, ci) element (up to 576 of them) over a 16 x 16 tile
+// staged in LDS, one slab per persistent workgroup -> wgrad_reduce (fixed order, deterministic).
+__global__ __launch_bounds__(256) void himage_wgrad_kernel(const _Float16* __restrict__ dZ, long ldz, const float* __restrict__ X,
+                                                          long ldx, int K, int NB, int H, int W, float* __restrict__ partial) {
+  constexpr int TH = 16, TW = 16, HW_ = TW + 2, NP = (TH + 2) * HW_;
+  __shared__ float Xs[4][NP];
+  __shared__ __attribute__((aligned(32))) float Zs[256 * 16];     // dZ tile [pixel][co], zero outside the image
+  const int tid = threadIdx.x;
+  const int n_out = 144 * K;                                      // element o = co + 16 * (tap + 9 * ci)
+  int zo[3], xo[3], ck[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int o = tid + 256 * j, oo = o < n_out ? o : 0;
+    const int co = oo & 15, tc = oo >> 4, tap = tc % 9, ci = tc / 9;
+    zo[j] = co; ck[j] = ci; xo[j] = (tap / 3) * HW_ + tap % 3;
+  }
+  float acc[3] = {0.f, 0.f, 0.f};
+  const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
+  const long n_tiles = (long)NB * tiles_y * tiles_x;
+  for (long t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const int tx = t % tiles_x; const long r = t / tiles_x; const int ty = r % tiles_y; const int nb = r / tiles_y;
+    __syncthreads();
+    for (int u = tid; u < NP * K; u += 256) {
+      const int k = u % K, hp = u / K, hy = hp / HW_, hx = hp % HW_;
+      const int gy = ty * TH + hy - 1, gx = tx * TW + hx - 1;
+      Xs[k][hp] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? X[(((long)nb * H + gy) * W + gx) * ldx + k] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int u = tid + 256 * i, p = u >> 1, q = u & 1;
+      const int gy = ty * TH + (p >> 4), gx = tx * TW + (p & 15);
+      f32x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (gy < H && gx < W) v = ldv<_Float16, 8>(dZ + (((long)nb * H + gy) * W + gx) * ldz + 8 * q);
+      *reinterpret_cast<f32x8*>(&Zs[p * 16 + 8 * q]) = v;
+    }
+    __syncthreads();
+    for (int p = 0; p < 256; ++p) {
+      const int hp = (p >> 4) * HW_ + (p & 15);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) acc[j] = __builtin_fmaf(Zs[p * 16 + zo[j]], Xs[ck[j]][hp + xo[j]], acc[j]);
+    }
+  }
+  // slab [tap][16][16] of this workgroup (layout of the generic kernels; ci >= K is never read)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int o = tid + 256 * j;
+    if (o < n_out) {
+      const int co = o & 15, tc = o >> 4, tap = tc % 9, ci = tc / 9;
+      partial[(((long)blockIdx.x * 9 + tap) * 16 + co) * 16 + ci] = acc[j];
+    }
+  }
+}
+
 template <typename T>
 static int colsum_impl(const T* X, long ldx, long M, int C, float* ws, float* out, int accumulate, void* stream) {
   ARCO_CHECK_ARG(X && ws && out && M > 0 && C > 0 && ldx >= C && (accumulate == 0 || accumulate == 1));
@@ -1107,6 +1161,23 @@ int arco_conv3d_wgrad_pro(const float* dZ, long ld_dz, int Cout, const float* in
 int arco_conv_wgrad(const float* dZ, long ld_dz, int Cout, const float* in, long ld_in, int Cin, int taps, int NB,
                     int H, int W, float* ws, float* dW, int accumulate, void* stream) {
   return arco_conv3d_wgrad(dZ, ld_dz, Cout, in, ld_in, Cin, taps, NB, 1, H, W, ws, dW, accumulate, 0, stream);
+}
+
+// dW [16][K][3][3] (+)= sum_pix dZ (f16, 16 channels) x in (fp32 image); ws sized by arco_wgrad_ws_floats(16, K, 9, NB * H * W)
+int arco_conv3x3_image_wgrad_h(const void* dZ, long ld_dz, int Cout, const float* in, long ld_in, int K, int NB, int H, int W,
+                               float* ws, float* dW, int accumulate, void* stream) {
+  ARCO_CHECK_ARG(dZ && in && ws && dW && K >= 1 && K <= 4 && ld_in >= K && NB > 0 && H > 0 && W > 0 && Cout > 0 && ld_dz >= Cout &&
+                 (accumulate == 0 || accumulate == 1));
+  arco_note_wgrad_route(0);
+  WgradPlan p;       // (the slab count never exceeds what arco_wgrad_ws_floats reserves: wgrad_plan clamps it)
+  const int rc = wgrad_plan(1, 9, NB, 1, H, W, K, Cout, ld_dz, ld_in, 4, false, 0, (reinterpret_cast<uintptr_t>(dZ) & 15) == 0, p);
+  if (rc != ARCO_OK) return rc;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(himage_wgrad_kernel, dim3((unsigned)p.slabs), dim3(256), 0, st, reinterpret_cast<const _Float16*>(dZ), ld_dz, in,
+                     ld_in, K, NB, H, W, ws);
+  arco_note_wgrad_route(p.route);
+  launch_wgrad_reduce(st, ws, (int)p.slabs, 9, p.CoutPad, p.CinPad, Cout, K, dW, accumulate);
+  return arco_launch_status();
 }
 
 // out[c] (+)= sum over pixels of X[pix][c];  ws holds 1024*C floats

@@ -42,11 +42,6 @@ def _wgrad(dy, x, like):
     return ops.conv_wgrad(dy, dy.stride(0), int(dy.shape[1]), x, x.stride(0), int(x.shape[1]), 1, 1, 1, n, like)
 
 
-def _h(name, t):
-    """entry point `name` for a feature map read as rows: its f16-`hi` form when the map is stored as f16 (ops.fm_rows_half)."""
-    return name + "_h" if t.dtype == torch.float16 else name
-
-
 def _fm_grad_buffer(half, ptr, shape, dev):
     """(fp32 scatter target [nb, *spatial, c], done(idx, n) -> the gradient to hand back) of a feature map read as rows: the f16
     form of the producer's gradient carrying ops.LOSS_SCALE for a map stored as f16 (_row_grad_buffer_h), else the target itself
@@ -219,14 +214,14 @@ def _rows2d(lo, maps, feas, pix):
     (r, ld), m = rv[0], int(idx[0].shape[0])
     k = int(lo.shape[1]) + int(maps[0].shape[1])
     X = torch.empty((m, k), dtype=torch.float32, device=dev)
-    L.call(_h("arco_gather_upcat_rows", r), L.ptr(lo_r), ldlo, *lo.shape[1:], L.ptr(r), ld, *maps[0].shape[1:], L.ptr(idx[0]), m,
+    L.call(L.h("arco_gather_upcat_rows", r), L.ptr(lo_r), ldlo, *lo.shape[1:], L.ptr(r), ld, *maps[0].shape[1:], L.ptr(idx[0]), m,
            L.ptr(X), k)
     Xs = [X]
     for i in range(1, nl):
         (r, ld), m, c = rv[i], int(idx[i].shape[0]), int(maps[i].shape[1])
         Xp = _fea_rows(X, feas[i - 1], 0)                     # fea_i(x)+x rows
         X = torch.empty((m, k + c), dtype=torch.float32, device=dev)
-        L.call(_h("arco_lerp4_cat_rows", r), L.ptr(Xp), k, k, L.ptr(lylx[i]), L.ptr(r), ld, c, L.ptr(idx[i]), m, L.ptr(X), k + c)
+        L.call(L.h("arco_lerp4_cat_rows", r), L.ptr(Xp), k, k, L.ptr(lylx[i]), L.ptr(r), ld, c, L.ptr(idx[i]), m, L.ptr(X), k + c)
         Xs.append(X)
         k += c
     return Xs, idx, lylx
@@ -311,21 +306,21 @@ def _rows3d(lo, maps, feas, pix):
     (r, ld), m = rv[0], int(at.shape[0])
     k = int(lo.shape[1]) + int(maps[0].shape[1])
     X = torch.empty((m, k), dtype=torch.float32, device=dev)
-    L.call(_h("arco_gather_upcat_rows3d", r), L.ptr(lo_r), ldlo, *lo.shape[1:], L.ptr(r), ld, *maps[0].shape[1:], L.ptr(at), m,
+    L.call(L.h("arco_gather_upcat_rows3d", r), L.ptr(lo_r), ldlo, *lo.shape[1:], L.ptr(r), ld, *maps[0].shape[1:], L.ptr(at), m,
            L.ptr(X), k)
     Xs = [X]
     if three:
         (r, ld), c = rv[1], int(maps[1].shape[1])
         Xp = _fea_rows(X, feas[0], 0)
         X = torch.empty((n, k + c), dtype=torch.float32, device=dev)
-        L.call(_h("arco_lerp8_cat_rows3d", r), L.ptr(Xp), k, k, *maps[0].shape[2:], L.ptr(r), ld, *maps[1].shape[1:], L.ptr(pix), n,
+        L.call(L.h("arco_lerp8_cat_rows3d", r), L.ptr(Xp), k, k, *maps[0].shape[2:], L.ptr(r), ld, *maps[1].shape[1:], L.ptr(pix), n,
                L.ptr(X), k + c)
         Xs.append(X)
         k += c
     (r, ld), c = rv[-1], int(maps[-1].shape[1])
     X4 = torch.empty((n, k + c), dtype=torch.float32, device=dev)
     X4[:, :k] = _fea_rows(X, feas[-2], 0)
-    L.call(_h("arco_gather_rows", r), L.ptr(r), ld, c, None, L.ptr(pix), None, 0, n, L.ptr(X4[:, k:]), k + c)
+    L.call(L.h("arco_gather_rows", r), L.ptr(r), ld, c, None, L.ptr(pix), None, 0, n, L.ptr(X4[:, k:]), k + c)
     return Xs + [X4], idx8, w8
 
 
@@ -427,7 +422,7 @@ def _class_weights(pl):
 
 def _wsum(rows, ld, wt, ldw, n_rows, C, D, totals, out, ldo):
     ws = torch.empty(L.query("arco_proto_ws_floats", n_rows, C, D), dtype=torch.float32, device=rows.device)
-    fn = "arco_weighted_row_sum_h" if rows.dtype == torch.float16 else "arco_weighted_row_sum"      # (f16 activation storage)
+    fn = L.h("arco_weighted_row_sum", rows)      # (f16 activation storage)
     L.call(fn, L.ptr(rows), ld, L.ptr(wt), ldw, n_rows, C, D, L.ptr(totals), L.ptr(ws), L.ptr(out), ldo)
 
 

@@ -10,7 +10,7 @@ conv3x3 (fp32 MFMA implicit GEMM, BN partial statistics fused in the epilogue) -
 BN finalize -> one fused BN-apply + LeakyReLU + dropout pass.
 
 With ops.ACT_HALF (train_arco_2d --act_dtype f16) a TRAINING-mode forward keeps every activation and activation gradient of the
-network as f16 (csrc/conv_h.hip, csrc/unet_h.hip, the *_h entry points): the first layer reads the fp32 image and writes f16, the
+network as f16 (csrc/conv_h.hip, the *_h entry points): the first layer reads the fp32 image and writes f16, the
 logits and the feature maps leave as fp32 (ops.from_half, whose backward applies the loss scale).  The two stages of a ConvBlock
 and the pooling run as separate passes there (no consumer-side activation in f16; the pooled apply kernel in f16 serves inference).
 Evaluation-mode forwards stay on the fp32 route whatever ops.ACT_HALF says.  F16 INFERENCE is opt-in and scoped: inside

@@ -588,7 +588,7 @@ def conv_raw(xr, ld, k, wp, n, nb, h, w, taps, bias=None, residual=None, ld_res=
     if outr is None:
         outr, ld_out = out, n
     mma = 0
-    image_h = False         # the U-Net's first layer in f16 mode: fp32 image in, f16 out (csrc/unet_h.hip)
+    image_h = False         # the U-Net's first layer in f16 mode: fp32 image in, f16 out (conv3x3_image_kernel<_Float16>)
     if half:
         if residual is not None:
             raise RuntimeError("arco_amd: f16 activation storage covers convolutions without a residual operand")
@@ -779,7 +779,7 @@ def _grad_into(param, compute):
 def colsum(xr, ld, m, c):
     ws = torch.empty(1024 * c, dtype=torch.float32, device=xr.device)
     out = torch.empty(c, dtype=torch.float32, device=xr.device)
-    L.call("arco_colsum_h" if _is_half(xr) else "arco_colsum", L.ptr(xr), ld, m, c, L.ptr(ws), L.ptr(out), 0)
+    L.call(L.h("arco_colsum", xr), L.ptr(xr), ld, m, c, L.ptr(ws), L.ptr(out), 0)
     return out
 
 
@@ -917,7 +917,7 @@ class ConvFn(torch.autograd.Function):
 def _bn_apply(zr, ldz, m, co, mean, istd, gamma, beta, slope, drop_mode, p, seed, P, out, ld_out=None, groups=1):
     seed_dev = SEED_DEV if (p > 0 and torch.cuda.is_current_stream_capturing()) else None
     _work(2 * m * co * (2 if _is_half(zr) else 4))
-    L.call("arco_bn_act_fwd_h" if _is_half(zr) else "arco_bn_act_fwd", L.ptr(zr), ldz, m, co, L.ptr(mean), L.ptr(istd),
+    L.call(L.h("arco_bn_act_fwd", zr), L.ptr(zr), ldz, m, co, L.ptr(mean), L.ptr(istd),
            L.ptr(gamma), L.ptr(beta), float(slope), int(drop_mode), float(p), seed, P, L.ptr(out), co if ld_out is None else ld_out,
            L.ptr(seed_dev), groups)
     return seed_dev
@@ -938,7 +938,7 @@ def _bn_backward(da, z, mean, istd, gamma, beta, slope, drop_mode, p, seed, P, s
     dz = new_act_nd(int(z.shape[0]), co, tuple(int(v) for v in z.shape[2:]), da.device, zr.dtype)
     dg_t, db_t, acc, dgamma, dbeta = _affine_grad_targets(gamma, beta) if gamma is not None else (None, None, 0, None, None)
     _work(5 * m * co * (2 if half else 4), 0.0, 3)     # reduce: dA, Z; apply: dA, Z -> dZ (algorithmic: dA, Z -> dZ would be 3)
-    L.call("arco_bn_act_bwd_h" if half else "arco_bn_act_bwd", L.ptr(dar), ldd, L.ptr(zr), ldz, m, co, L.ptr(mean), L.ptr(istd),
+    L.call(L.h("arco_bn_act_bwd", half), L.ptr(dar), ldd, L.ptr(zr), ldz, m, co, L.ptr(mean), L.ptr(istd),
            L.ptr(gamma), L.ptr(beta), slope, drop_mode, p, seed, P, L.ptr(ws), L.ptr(dg_t), L.ptr(db_t), acc, L.ptr(dz), co,
            L.ptr(seed_dev), groups)
     return dz, dgamma, dbeta
@@ -957,7 +957,7 @@ def _batch_stats(rows, ld, m, c, G):
     nblk = L.query("arco_chan_stats_blocks", m // G)
     ssum = torch.empty((c, G * nblk), dtype=torch.float32, device=rows.device)
     ssq = torch.empty((c, G * nblk), dtype=torch.float32, device=rows.device)
-    L.call("arco_chan_stats_h" if _is_half(rows) else "arco_chan_stats", L.ptr(rows), ld, m, c, L.ptr(ssum), L.ptr(ssq), G)
+    L.call(L.h("arco_chan_stats", rows), L.ptr(rows), ld, m, c, L.ptr(ssum), L.ptr(ssq), G)
     return ssum, ssq, nblk
 
 
@@ -1274,7 +1274,7 @@ class BnActFn(torch.autograd.Function):
             if gamma is None or p > 0 or residual.dtype != z.dtype or tuple(residual.shape) != tuple(z.shape):
                 raise RuntimeError("arco_amd: bn_act(residual=...) is the dropout-free BatchNorm apply with a same-shape, same-dtype addend")
             rr, ldr = rows_view(residual)
-            L.call("arco_bn_act_add_fwd_h" if _is_half(zr) else "arco_bn_act_add_fwd", L.ptr(zr), ldz, m, co, L.ptr(mean), L.ptr(istd),
+            L.call(L.h("arco_bn_act_add_fwd", zr), L.ptr(zr), ldz, m, co, L.ptr(mean), L.ptr(istd),
                    L.ptr(gamma), L.ptr(beta), float(slope), L.ptr(rr), ldr, L.ptr(a), co, G)
             ctx.seed_dev = None
         else:
@@ -1319,7 +1319,7 @@ class BnActD2sFn(torch.autograd.Function):
             if residual.dtype != y.dtype or tuple(residual.shape) != tuple(a.shape):
                 raise RuntimeError("arco_amd: bn_act_d2s(residual=...) needs an addend of the activation's shape and dtype")
             rr, ldr = rows_view(residual)
-        L.call("arco_bn_act_d2s_fwd_h" if half else "arco_bn_act_d2s_fwd", L.ptr(yr), m8, c, L.ptr(mean), L.ptr(istd), L.ptr(gamma),
+        L.call(L.h("arco_bn_act_d2s_fwd", half), L.ptr(yr), m8, c, L.ptr(mean), L.ptr(istd), L.ptr(gamma),
                L.ptr(beta), float(slope), L.ptr(rr), ldr, L.ptr(a), c, x2, y2, z2, G)
         ctx.save_for_backward(y, mean, istd, gamma, beta)
         ctx.cfg = (float(slope), G, nblk, residual is not None)
@@ -1341,7 +1341,7 @@ class BnActD2sFn(torch.autograd.Function):
         dy = new_act_nd(n, c8, (x2, y2, z2), y.device, yr.dtype)
         ws = torch.empty(G * (2 * c * nblk + 2 * c), dtype=torch.float32, device=y.device)
         dg_t, db_t, acc, dgamma, dbeta = _affine_grad_targets(gamma, beta)
-        L.call("arco_bn_act_d2s_bwd_h" if half else "arco_bn_act_d2s_bwd", L.ptr(dar), ldd, L.ptr(yr), yr.shape[0] * 8, c, L.ptr(mean),
+        L.call(L.h("arco_bn_act_d2s_bwd", half), L.ptr(dar), ldd, L.ptr(yr), yr.shape[0] * 8, c, L.ptr(mean),
                L.ptr(istd), L.ptr(gamma), L.ptr(beta), slope, L.ptr(ws), L.ptr(dg_t), L.ptr(db_t), acc, L.ptr(dy), x2, y2, z2, G)
         return dy, dgamma, dbeta, None, None, None, None, None, None, (da if has_res else None)
 
@@ -1389,7 +1389,7 @@ class S2dSkipFn(torch.autograd.Function):
         pr, ldp = rows_view(dxs)
         ar, lda = rows_view(dskip)
         out = new_act_nd(n, c, ctx.shape[2:], dxs.device, pr.dtype)
-        L.call("arco_d2s3_add_h" if _is_half(pr) else "arco_d2s3_add", L.ptr(pr), ldp, n, x2, y2, z2, c, L.ptr(ar), lda, L.ptr(out), c)
+        L.call(L.h("arco_d2s3_add", pr), L.ptr(pr), ldp, n, x2, y2, z2, c, L.ptr(ar), lda, L.ptr(out), c)
         return out
 
 
@@ -1444,7 +1444,7 @@ def _maxpool2_forward(x):
     """maxpool2 of a channels-last activation; follows x's storage type (fp32 / f16)."""
     xr, ld, nb, c, h, w = _geom(x)
     y = new_act_nd(nb, c, (h // 2, w // 2), x.device, xr.dtype)
-    L.call("arco_maxpool2_fwd_h" if _is_half(xr) else "arco_maxpool2_fwd", L.ptr(xr), ld, nb, h, w, c, L.ptr(y), c)
+    L.call(L.h("arco_maxpool2_fwd", xr), L.ptr(xr), ld, nb, h, w, c, L.ptr(y), c)
     return y
 
 
@@ -1460,10 +1460,10 @@ def _maxpool2_backward(xr, ld, nb, h, w, c, dy, dskip):
     esz = 2 if half else 4
     _work((nb * h * w * (3 if dskip is not None else 2) + nb * h * w // 4) * c * esz)
     if dskip is None:
-        L.call("arco_maxpool2_bwd_h" if half else "arco_maxpool2_bwd", L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy, L.ptr(dx), c)
+        L.call(L.h("arco_maxpool2_bwd", half), L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy, L.ptr(dx), c)
     else:
         sr, lds = rows_view(dskip)
-        L.call("arco_maxpool2_bwd_add_h" if half else "arco_maxpool2_bwd_add", L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy,
+        L.call(L.h("arco_maxpool2_bwd_add", half), L.ptr(xr), ld, nb, h, w, c, L.ptr(dyr), ldy,
                L.ptr(sr), lds, L.ptr(dx), c)
     return dx
 
@@ -1508,7 +1508,7 @@ def _bilinear_forward(xr, ld, nb, h, w, c, ho, wo, out, ld_out):
     """align_corners bilinear resize of rows xr into `out` (a channels-last tensor or channel slice); follows xr's storage type."""
     half = _is_half(xr)
     _work(nb * c * (h * w + ho * wo) * (2 if half else 4))
-    L.call("arco_bilinear_fwd_h" if half else "arco_bilinear_fwd", L.ptr(xr), ld, nb, h, w, c, ho, wo, L.ptr(out), ld_out)
+    L.call(L.h("arco_bilinear_fwd", half), L.ptr(xr), ld, nb, h, w, c, ho, wo, L.ptr(out), ld_out)
 
 
 def _bilinear_backward(dyr, ldy, nb, h, w, c, ho, wo):
@@ -1747,7 +1747,7 @@ def bn_act_eval(z, gamma, beta, running_mean, running_var, slope=0.0, eps=1e-5):
             P *= v
         istd = torch.rsqrt(running_var + eps)
         a = new_act_nd(int(z.shape[0]), co, sp, z.device, zr.dtype)
-        L.call("arco_bn_act_fwd_h" if _is_half(zr) else "arco_bn_act_fwd", L.ptr(zr), ldz, zr.shape[0], co, L.ptr(running_mean),
+        L.call(L.h("arco_bn_act_fwd", zr), L.ptr(zr), ldz, zr.shape[0], co, L.ptr(running_mean),
                L.ptr(istd), L.ptr(gamma), L.ptr(beta), float(slope), 0, 0.0, 0, P, L.ptr(a), co, None, 1)
         return a
 

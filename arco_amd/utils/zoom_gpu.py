@@ -102,7 +102,7 @@ def argmax_zoom_back(logits, out_size):
     if C > MAX_CLASSES:
         raise ValueError(f"at most {MAX_CLASSES} classes, got {C}")
     r, ld = rows_view(logits.detach())                       # float32 or float16 rows (any other dtype arrives as float32)
-    entry = "arco_argmax_zoom_back2d_h" if r.dtype == torch.float16 else "arco_argmax_zoom_back2d"     # f16 rows are read as stored
+    entry = L.h("arco_argmax_zoom_back2d", r)     # f16 rows are read as stored
     out = torch.empty((n, N0, N1), dtype=torch.int64, device=logits.device)
     with torch.cuda.device(logits.device):
         L.call(entry, L.ptr(r), ld, C, n, P0, P1, N0, N1, _step(P0, N0), _step(P1, N1), L.ptr(out))

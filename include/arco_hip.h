@@ -679,7 +679,7 @@ int arco_d2s3_add(const float* P, long ldp, int NV, int X2, int Y2, int Z2, int 
 int arco_d2s3_add_h(const void* P, long ldp, int NV, int X2, int Y2, int Z2, int C, const void* ADD, long lda, void* V, long ldv, void* stream);
 int arco_cast_h2f(const void* x, long n, float* y, void* stream);
 int arco_cast_f2h(const float* x, long n, float scale, void* y, void* stream);
-/* f16 activation storage on the 2-D path (train_arco_2d --act_dtype f16; csrc/unet_h.hip).  The 3x3 convolutions of f16 maps run
+/* f16 activation storage on the 2-D path (train_arco_2d --act_dtype f16; the _Float16 instantiations of csrc/elementwise.hip).  The 3x3 convolutions of f16 maps run
  * through arco_conv3d_fwd / arco_conv3d_wgrad(taps = 9, D3 = 1, mma = 4): hconv_kernel's plane step without the depth loop, rows
  * that are not whole 16-byte pieces (the gradient of a 4- / 19-class out_conv) staged element-wise.
  *   arco_conv3x3_image_fwd_h:    the first layer - fp32 image (K <= 4 channels, the fp32 forward pack [9][16][16]) -> f16 map of

@@ -1,6 +1,6 @@
 """References and cases for the two kernels of the f16 inference route (`ops.eval_half`):
 
-  arco_bn_act_pool_fwd_h (csrc/unet_h.hip)      ref_bn_act_pool: the pooled BatchNorm apply pass on f16 storage
+  arco_bn_act_pool_fwd_h (csrc/elementwise.hip) ref_bn_act_pool: the pooled BatchNorm apply pass on f16 storage
   arco_argmax_zoom_back2d_h (csrc/zoom.hip)     ref_argmax_zoom_back: the arg-max of f16 logit rows, zoomed back by order 0
 
 ref_bn_act_pool restates bn_act_fwd_kernel<_Float16>'s arithmetic operation for operation: in fp32 t = z - mean, u = t * istd,

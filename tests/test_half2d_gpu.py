@@ -1,4 +1,4 @@
-"""f16 ACTIVATION STORAGE of the 2-D path (train_arco_2d --act_dtype f16; csrc/conv_h.hip's 2-D dispatch, csrc/unet_h.hip, the *_h
+"""f16 ACTIVATION STORAGE of the 2-D path (train_arco_2d --act_dtype f16; csrc/conv_h.hip's 2-D dispatch, the _Float16 kernels of csrc/elementwise.hip, the *_h
 entry points) against the fp32 kernels of the same operators AND float64 PyTorch on the CPU, on the SAME f16-representable inputs -
 the convention of tests/test_half_gpu.py: products of f16 values are exact in fp32 and accumulation is fp32 in both, so what differs
 is one rounding of each stored result (2^-11 relative): stored results are held to 1e-3 of the tensor's maximum, fp32 weight / bias

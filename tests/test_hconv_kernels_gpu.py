@@ -32,7 +32,7 @@ Routes (taps, id), covered / not covered, and why:
          ld_in % 8 != 0, the output 8 bytes off a 16-byte boundary) that must report hconv_kernel<1,256,16> / <1,128,32>.
   conv3d_image_kernel<3> in mma 4   27701016: one plane smaller than a tile, and two volumes in two groups, both with statistics: covered.
   One data-gradient case (mode 1 | 4 pack) per kernel template against float64 autograd.
-  Out of scope: hwgrad_kernel and the casts (tests/test_wgrad_kernels_gpu.py, tests/test_side_kernels_gpu.py), unet_h.hip.
+  Out of scope: hwgrad_kernel and the casts (tests/test_wgrad_kernels_gpu.py, tests/test_side_kernels_gpu.py), the f16 pooling / resize / first-layer kernels.
 The cases that need 256 workgroups, 65536 rows or more units than slots are as large as that takes and no larger (the largest, 270336
 voxels of 16 channels, takes under a second with its float64 reference); EVERY case runs all four kinds.
 

@@ -25,7 +25,8 @@ def _ac_src(n_out, n_in):
 
 
 def emulate_resize(x, ho, wo, mode):
-    """bilinear_fwd_kernel / hbilinear_fwd_kernel: hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11) in fp32."""
+    """bilinear_fwd_kernel<T, V>: hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11) in fp32.  The kernel forms it with bl_blend1,
+    fma(ly, fma(lx, v11, hx * v10), hy * fma(lx, v01, hx * v00)), for both storage types; here every operation rounds."""
     y0, y1, ly = _ac_src(ho, x.shape[2])
     x0, x1, lx = _ac_src(wo, x.shape[3])
     ly, lx = ly.view(-1, 1), lx.view(1, -1)
@@ -45,7 +46,7 @@ def _adjoint_weights(n_out, n_in):
 
 
 def emulate_resize_adjoint(dy, hi, wi, mode):
-    """bilinear_bwd_kernel / hbilinear_bwd_kernel: dx[yi, xi] = sum wy * wx * dy[yo, xo] in fp32 (here: rows, then columns)."""
+    """bilinear_bwd_kernel<T, V>: dx[yi, xi] = sum wy * wx * dy[yo, xo] in fp32 (here: rows, then columns)."""
     wy, wx = _adjoint_weights(dy.shape[2], hi), _adjoint_weights(dy.shape[3], wi)
     return _round(torch.einsum("pi,ncpj->ncij", wy, torch.einsum("qj,ncpq->ncpj", wx, dy)), mode)
 

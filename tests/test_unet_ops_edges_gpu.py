@@ -1,6 +1,6 @@
 """The U-Net operators AROUND the convolutions - nn.MaxPool2d(2) (+ the skip gradient), the align_corners bilinear resize (+ the
 in-place concat) and the first layer (3x3 convolution of the fp32 image, <= 4 channels -> 16) - in both storage modes (fp32 and f16
-activation storage: csrc/elementwise.hip, csrc/unet_h.hip, the image kernels of csrc/igemm.hip), each against plain PyTorch on the CPU
+activation storage: csrc/elementwise.hip, the image kernels of csrc/igemm.hip and csrc/wgrad.hip), each against plain PyTorch on the CPU
 in float64 on the same input values, at the edges the other operator tests do not reach: tied maxima, operands that are channel
 slices of a wider buffer, sides of 1 / identity / downsampling resizes with a random gradient, every channel count and ragged tiles
 of the first layer, per-group BatchNorm statistics, and grids large enough for the second trip of the grid-stride loops.
@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 U32, U16, SUB16 = 2.0 ** -24, 2.0 ** -11, 2.0 ** -25
-GRID_CAP = 4096 * 256          # ew_grid / uh_grid: at most 4096 workgroups of 256 threads
+GRID_CAP = 4096 * 256          # ew_grid: at most 4096 workgroups of 256 threads
 
 MODES = ("f", "h")             # fp32 tensors | f16 activation storage
 

@@ -1,4 +1,4 @@
-"""Every weight- and bias-gradient route of csrc/wgrad.hip, conv_h.hip and unet_h.hip called DIRECTLY through arco_amd._lib
+"""Every weight- and bias-gradient route of csrc/wgrad.hip and conv_h.hip called DIRECTLY through arco_amd._lib
 (arco_conv_wgrad, arco_conv3d_wgrad, arco_conv3d_wgrad_pro, arco_conv3x3_image_wgrad_h, arco_colsum, arco_colsum_h, arco_transpose2d),
 one route per test, against the float64 reference of tests/wgrad_kernel_refs.py computed from the same fp32 / f16 operand values.
 Every test asserts the kernel that ran through arco_wgrad_last_route and the same id, slab count, slab size and reduction kernel

@@ -1,5 +1,5 @@
 """Cases, inputs, float64 references, per-element bounds and comparison helpers shared by tests/test_wgrad_kernels_gpu.py (every
-weight-gradient route of csrc/wgrad.hip, conv_h.hip and unet_h.hip, the slab reductions, arco_colsum(_h) and arco_transpose2d, one route
+weight-gradient route of csrc/wgrad.hip and conv_h.hip, the slab reductions, arco_colsum(_h) and arco_transpose2d, one route
 per test, called directly) and tests/test_wgrad_kernels_cpu.py (the routes asserted through arco_wgrad_config, the slab sweep, the
 input conditions, an fp32 emulation of the wide kind inside the same bounds, planted errors, the host-side rejections).  Plain CPU
 torch / numpy only; nothing here touches a GPU.
