@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "arco_hip.h"   // include/arco_hip.h, the C ABI: every extern "C" definition is checked against its declaration there
 
 #define ARCO_OK 0
 #define ARCO_ERR_ARG (-1)

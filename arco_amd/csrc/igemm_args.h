@@ -1,19 +1,15 @@
 // Argument block, consumer-side activation loaders, route word and dispatch declarations of the forward / data-gradient
 // convolution kernels (igemm.hip, conv_sp.hip, conv3d_fl.hip, gemm_sp.hip, conv_h.hip).
 #pragma once
+#include <stddef.h>
 #include "common.h"
 
 // Flat-position 3x3 tiles (igemm_kernel FLAT, wgrad_halo2_kernel FLAT) stage planes with a padded row stride W + 2 up to this bound
 constexpr int IGEMM_FLAT_WPMAX = 64;
 
-// include/arco_hip.h: ArcoActPro (the C-ABI descriptor of a consumer-side activation); repeated here for the kernels
-struct ArcoActPro {
-  const float* mean; const float* istd; const float* gamma; const float* beta;   // [groups][K] statistics, [K] affine parameters
-  float slope;                       // LeakyReLU slope (0: ReLU)
-  int groups;                        // BatchNorm groups of the producing layer: images [g*NB/G, (g+1)*NB/G) use statistics row g
-  int drop_mode; float p;            // 0: none; 1: nn.Dropout(p) with the stateless mask of bn_act_fwd_kernel
-  unsigned long long seed; const unsigned long long* seed_dev;
-};
+// ArcoActPro, the C-ABI descriptor of a consumer-side activation, is include/arco_hip.h's (common.h): the kernels read the caller's
+// struct as it is passed, and arco_amd/_lib.py mirrors the same layout for ctypes
+static_assert(sizeof(ArcoActPro) == 64 && offsetof(ArcoActPro, seed) == 48, "ArcoActPro: four pointers, four 4-byte scalars, uint64, pointer");
 
 struct IgemmArgs {
   const float* A; long lda;

@@ -25,6 +25,7 @@
 #include <deque>
 #include <functional>
 #include <unistd.h>
+#include "arco_hip.h"   // the declarations of the host entry points defined here (this file does not reach common.h)
 
 namespace {
 constexpr int MT_N = 624, MT_M = 397;

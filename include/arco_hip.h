@@ -4,7 +4,14 @@
  * The reference (charlesyou999648/ARCO) is pure Python/PyTorch: it has no FFI layer, so the
  * "interface each entry point replaces" is the PyTorch call sequence at the cited reference
  * file:line (paths relative to the reference's code/ directory).  The Python host
- * (arco_amd/*.py) binds these with ctypes (arco_amd/_lib.py); INTEGRATION.md shows the stub.
+ * (the modules of arco_amd) binds these with ctypes (arco_amd/_lib.py); INTEGRATION.md shows the stub.
+ *
+ * This file is the one definition of the ABI: it is compiled into every source of arco_amd/csrc (common.h includes it, so a
+ * definition that disagrees with its declaration does not build), and arco_amd/_lib.py parses it at import into the ctypes
+ * argtypes / restype of every entry point.  A new entry point is written twice - its definition and its declaration here -
+ * and the compiler compares the two.  For the parser's sake a declaration is `<ret> arco_<name>(<params>);` with scalar
+ * parameters of type int, long, float, double or uint64_t, anything else behind a pointer, and `void* stream` last where
+ * the entry point enqueues work.
  *
  * Conventions
  *  - plain pointers and sizes only; every pointer is DEVICE memory owned by the caller
@@ -237,7 +244,9 @@ int arco_wgrad_last_route(void);
  *     a = dropout(lrelu((z - mean) * istd * gamma + beta))
  * element by element in their loaders while they stage z for the matrix cores (conv_sp.hip producer waves, wgrad_split_kernel): the
  * activation never exists in HBM (2 of the 4 HBM crossings of every such activation, and one launch per stage, are gone).  The
- * arithmetic is arco_bn_act_fwd's operation for operation: results are bit-identical to the two-pass route.                        */
+ * arithmetic is arco_bn_act_fwd's operation for operation: results are bit-identical to the two-pass route.
+ * The struct below is the kernels' own definition (csrc/igemm_args.h asserts its 64 bytes, seed at 48); arco_amd/_lib.py ActPro
+ * mirrors it field for field.                                                                                                      */
 typedef struct ArcoActPro {
   const float* mean; const float* istd;   /* [groups][K] batch statistics of the producing layer (arco_bn_finalize)                 */
   const float* gamma; const float* beta;  /* [K] nn.BatchNorm2d weight / bias                                                       */

@@ -2,6 +2,8 @@
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,6 +22,17 @@ def test_library_exports_header_symbols():
     assert {"arco_wgrad_config", "arco_wgrad_last_route"} <= declared      # ... and of the weight-gradient route, with its query
     assert isinstance(_lib.query("arco_wgrad_last_route"), int)
     assert _lib.query("arco_wgrad_config", 0, 9, 1, 1, 16, 16, 16, 16, 16, 16, 0, 0, 1, None, None, None) == 9201616
+
+
+def test_library_defines_only_declared_symbols():
+    """The other direction: every dynamic function symbol arco_* that the built library defines is declared in the header."""
+    from arco_amd import _lib
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
+    assert nm, "neither nm nor llvm-nm found: cannot read the library's symbols"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    defined = {f[2] for f in (ln.split() for ln in out.splitlines()) if len(f) == 3 and f[1] in "TW" and f[2].startswith("arco_")}
+    assert len(defined) > 100, len(defined)
+    assert defined == set(_lib.EXPORTS), defined ^ set(_lib.EXPORTS)      # EXPORTS: the header's declarations (the test above)
 
 
 def test_missing_library_fails_loudly(monkeypatch):

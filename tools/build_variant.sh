@@ -11,7 +11,7 @@ objs=""
 for s in $(sed -n 's/^SRCS *:= *//p' Makefile); do      # the translation units are the Makefile's
   s=${s%.hip}
   if [[ " $srcs " == *" $s.hip "* ]]; then
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-value $flags -c $s.hip -o ../../build/var_$name/$s.o
+    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -Wall -Wno-unused-function -Wno-unused-value $flags -c $s.hip -o ../../build/var_$name/$s.o
     objs="$objs ../../build/var_$name/$s.o"
   else
     objs="$objs $s.o"

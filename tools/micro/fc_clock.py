@@ -12,7 +12,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "build":
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     subprocess.check_call(["make", "-C", cs, "-j6"], stdout=subprocess.DEVNULL)
     obj = os.path.join(ROOT, "build", "conv3d_fl_clock.o")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-DARCO_FC_CLOCK", "-c",
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-DARCO_FC_CLOCK", "-c",
                            os.path.join(cs, "conv3d_fl.hip"), "-o", obj])
     objs = [os.path.join(cs, f"{n}.o") for n in ("loss_front", "igemm", "wgrad", "conv_sp", "gemm_sp", "conv_h", "elementwise", "det_scatter", "glue", "sampler_host", "augment")]
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", obj] + objs + ["-lpthread", "-o", os.path.join(ROOT, "build", "libarco_hip_fcclock.so")])

@@ -78,7 +78,7 @@ rep("""  hipLaunchKernelGGL(kern, dim3((unsigned)(mblocks < cus ? mblocks : cus)
 os.makedirs(os.path.join(root, "build"), exist_ok=True)
 open(os.path.join(root, "build/conv_sp_trace.hip"), "w").write(s)
 c = os.path.join(root, "arco_amd/csrc")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-value", "-Wno-uninitialized", "-DTRACE_BLOCK=7", "-c",
+subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(root, "include"), "-Wno-unused-value", "-Wno-uninitialized", "-DTRACE_BLOCK=7", "-c",
                        os.path.join(root, "build/conv_sp_trace.hip"), "-o", os.path.join(root, "build/conv_sp_trace.o")])
 objs = [os.path.join(c, f) for f in ("igemm.o", "wgrad.o", "loss_front.o", "elementwise.o", "glue.o", "sampler_host.o", "augment.o")]
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", os.path.join(root, "build/conv_sp_trace.o")] + objs + ["-lpthread", "-o", os.path.join(root, "build/libsptrace.so")])
