@@ -137,7 +137,7 @@ class MLP(nn.Module):
 
 class ISD(nn.Module):
     def __init__(self, K=48, m=0.99, Ts=0.1, Tt=0.01, num_classes=4, train_encoder=True, train_decoder=True,
-                 latent_pooling_size=1, latent_feature_size=256, output_pooling_size=16, patch_size=64, in_chns=1, patch_heads="torch"):
+                 latent_pooling_size=1, latent_feature_size=256, output_pooling_size=16, patch_size=64, in_chns=1, patch_heads="torch", kld="torch"):
         super(ISD, self).__init__()
         self.K, self.m, self.Ts, self.Tt = K, m, Ts, Tt
         self.num_classes = num_classes
@@ -145,6 +145,9 @@ class ISD(nn.Module):
         if patch_heads not in ("torch", "gpu", "fused"):
             raise ValueError(f"patch_heads is 'torch', 'gpu' or 'fused', got {patch_heads!r}")
         self.patch_heads = patch_heads          # the route of the patch-wise output heads (stage1.patch_heads)
+        if kld not in ("torch", "fused"):
+            raise ValueError(f"kld is 'torch' or 'fused', got {kld!r}")
+        self.kld = kld          # the route of the two KL-to-queue terms in the steppers (stage1.queue_kld)
         self.latent_feature_size = latent_feature_size
         self.model = create_model(num_classes=num_classes, train_encoder=train_encoder, train_decoder=train_decoder,
                                   in_chns=in_chns)

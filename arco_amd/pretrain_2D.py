@@ -9,7 +9,8 @@ the HIP kernels (arco_amd.ops), the optimizer is torch.optim.SGD(momentum=0.9, w
 reference); `--gpu_ingest 1` keeps the dataset in device memory and runs the student transform as HIP kernels, with the host
 route's random draws (dataloaders/gpu_ingest.py, dataloaders/stage1_aug.py); `--patch_heads gpu` pools the patches of the output
 heads in one HIP kernel each way (stage1.patch_heads, csrc/patch_pool.hip), `--patch_heads fused` runs their pointwise layers in the same
-kernels (csrc/patch_head.hip)."""
+kernels (csrc/patch_head.hip); `--kld fused` takes the two KL-divergence-to-queue terms from two HIP kernels over the cosine matrices
+(stage1.queue_kld, csrc/queue_kld.hip)."""
 import argparse
 import logging
 import os
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import glue, optim
+from . import glue, optim, stage1
 from .model_2D import ISD
 
 
@@ -68,6 +69,10 @@ def build_parser():
                         '(csrc/patch_pool.hip, stage1.patch_heads), whatever the patch and pooling sizes; fused: pooling and pointwise '
                         'layers in one HIP kernel each way, parameter gradients summed in float64 (csrc/patch_head.hip); torch: the '
                         'tensor-op route, patch by patch when the pooling windows do not tile the patch stride (the 3-D default, 20 and 8)')
+    p.add_argument('--kld', type=str, default='torch', choices=['torch', 'fused'],
+                   help='fused: each KL-divergence-to-queue term reads its two cosine matrices once forward and once backward, in two HIP '
+                        'kernels (csrc/queue_kld.hip, stage1.queue_kld), the queue normalised once for both sides; torch: the tensor-op '
+                        'route (compute_logits and KLD)')
     return p
 
 
@@ -128,7 +133,8 @@ class PretrainStep2D:
         return ISD(K=args.K, m=0.99, Ts=args.T_s, Tt=args.T_t, num_classes=args.num_classes,
                    latent_pooling_size=args.latent_pooling_size, latent_feature_size=args.latent_feature_size,
                    output_pooling_size=args.output_pooling_size, train_encoder=args.train_encoder,
-                   train_decoder=args.train_decoder, patch_size=args.cut_size, patch_heads=getattr(args, "patch_heads", "torch"))
+                   train_decoder=args.train_decoder, patch_size=args.cut_size, patch_heads=getattr(args, "patch_heads", "torch"),
+                   kld=getattr(args, "kld", "torch"))
 
     def __init__(self, args, device):
         self.args, self.device = args, device
@@ -146,12 +152,15 @@ class PretrainStep2D:
             student_batch = student_batch.unsqueeze(1)
         if teacher_batch.dim() == 3:
             teacher_batch = teacher_batch.unsqueeze(1)
-        outputs, ema_output, ema_latent_logits, latent_logits, ema_output_logits, output_logits = \
-            self.model(student_batch.float(), teacher_batch.float())
+        if self.model.kld == "torch":
+            outputs, ema_output, ema_latent_logits, latent_logits, ema_output_logits, output_logits = \
+                self.model(student_batch.float(), teacher_batch.float())
+            loss_latent = self.kld(inputs=latent_logits, targets=ema_latent_logits)
+            loss_output = self.kld(inputs=output_logits, targets=ema_output_logits)
+        else:          # no logits are built: both terms from stage1.queue_kld on the model's route
+            outputs, ema_output, loss_latent, loss_output = stage1.isd_kld_terms(self.model, student_batch.float(), teacher_batch.float())
         loss_ce, loss_dice = glue.supervised_loss(outputs[:a.labeled_bs], student_label[:a.labeled_bs].long())
         supervised_loss = self.sup_scale * (loss_dice + loss_ce)
-        loss_latent = self.kld(inputs=latent_logits, targets=ema_latent_logits)
-        loss_output = self.kld(inputs=output_logits, targets=ema_output_logits)
         if a.train_encoder == 1 and not a.train_decoder == 1:
             loss = a.k1 * loss_latent
         else:
@@ -221,6 +230,8 @@ def run_training(args, snapshot_path, stepper_cls, transform_student, build_load
         n_patches = int(np.prod([(s - m.patch_size) // step + 1 for s in args.patch_size]))
         logging.info("patch heads on the {} route: {} patches of size {} pooled to {}".format(args.patch_heads, n_patches, m.patch_size,
                                                                                              args.output_pooling_size))
+    if getattr(args, "kld", "torch") != "torch":
+        logging.info("KL-to-queue terms on the {} route".format(args.kld))
     if getattr(args, "gpu_ingest", 0):
         from .dataloaders import gpu_ingest, stage1_aug
         transform_student = stage1_aug.device_transform(transform_student)

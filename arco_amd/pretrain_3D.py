@@ -41,7 +41,7 @@ class PretrainStep3D(P2.PretrainStep2D):
                       latent_pooling_size=args.latent_pooling_size, latent_feature_size=args.latent_feature_size,
                       output_pooling_size=args.output_pooling_size, train_encoder=args.train_encoder,
                       train_decoder=args.train_decoder, patch_size=getattr(args, "head_patch", 20),
-                      patch_heads=getattr(args, "patch_heads", "torch"))
+                      patch_heads=getattr(args, "patch_heads", "torch"), kld=getattr(args, "kld", "torch"))
 
 
 def synthetic_batch(b, patch, n_cls, seed):

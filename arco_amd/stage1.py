@@ -233,17 +233,78 @@ def mlp(head, x):
     return F.linear(F.linear(y, m.f1.weight, m.f1.bias), m.f2.weight, m.f2.bias)
 
 
-def isd_forward(isd, im_q, im_k=None, Ts=None, Tt=None):
-    """Returns (outputs, ema_output, ema_latent_logits, latent_logits, ema_output_logits, output_logits) in training mode,
-    (outputs, latent) in eval mode.  The reshapes below are the reference's, view for view (they interleave patch and
-    batch indices; the queues are stored in the layout they produce).  The KEY heads are not under no_grad in the
-    reference (:268,282): they are EMA-updated and, being part of the KLD targets' graph, trained by the optimizer too."""
-    Ts = Ts if Ts else isd.Ts
-    Tt = Tt if Tt else isd.Tt
+class QueueKLDFn(torch.autograd.Function):
+    """F.kl_div(F.log_softmax(cs / Ts, 1), F.softmax(ct / Tt, 1), 'batchmean') of two fp32 matrices of raw cosines [N, L] as two kernels
+    (csrc/queue_kld.hip): the forward reads each matrix once and keeps the per-row statistics [N, 3] float64, the backward is
+    elementwise and writes each gradient OVER its cosine matrix - cs and ct are spent by it, the caller hands over matrices nobody else
+    reads (queue_kld's GEMM outputs), and a second backward through the same node raises.  The gradient of a side that needs none (a
+    detached teacher) is not computed."""
+
+    @staticmethod
+    def forward(ctx, cs, ct, Ts, Tt):
+        from . import _lib as L
+        L.require_gpu(cs, ct)
+        if cs.dtype != torch.float32 or ct.dtype != torch.float32 or cs.dim() != 2 or cs.shape != ct.shape or cs.numel() == 0:
+            raise ValueError(f"QueueKLDFn: two fp32 matrices [N, L] of one shape, got {cs.dtype} {tuple(cs.shape)} and {ct.dtype} {tuple(ct.shape)}")
+        if not (Ts > 0 and Tt > 0):
+            raise ValueError(f"QueueKLDFn: positive temperatures, got {Ts} and {Tt}")
+        cs, ct = cs.contiguous(), ct.contiguous()
+        N, Lq = cs.shape
+        stats = torch.empty((N, 3), dtype=torch.float64, device=cs.device)
+        loss = torch.empty((), dtype=torch.float32, device=cs.device)
+        ctx.args = (N, Lq, Lq, Lq, 1.0 / Ts, 1.0 / Tt)
+        L.call("arco_queue_kld_fwd", L.ptr(cs), L.ptr(ct), *ctx.args, L.ptr(stats), L.ptr(loss))
+        ctx.save_for_backward(cs, ct, stats)
+        ctx.spent = False
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _lib as L
+        if ctx.spent:
+            raise RuntimeError("QueueKLDFn: the first backward wrote the gradients over the cosine matrices; a second one through the same "
+                               "graph has nothing to read")
+        cs, ct, stats = ctx.saved_tensors
+        need_s, need_t = ctx.needs_input_grad[:2]
+        if not (need_s or need_t):
+            return None, None, None, None
+        ctx.spent = True
+        Lq = ctx.args[1]
+        g = g.detach().to(torch.float32).contiguous()
+        L.call("arco_queue_kld_bwd", L.ptr(cs), L.ptr(ct), *ctx.args, L.ptr(stats), L.ptr(g),
+               L.ptr(cs) if need_s else None, Lq, L.ptr(ct) if need_t else None, Lq)
+        return cs.detach() if need_s else None, ct.detach() if need_t else None, None, None
+
+
+KLD_ROUTES = ("torch", "fused")
+
+
+def queue_kld(z_student, z_teacher, queue, Ts, Tt, route="torch"):
+    """One KL-divergence-to-queue term of stage 1 (pretrain_2D.py:235-252): the batch-mean KL(softmax(teacher logits) || softmax(student
+    logits)) of the rows of z_student and z_teacher against the rows of the queue snapshot.
+    route="torch": KLD()(compute_logits(z_student, queue, Ts), compute_logits(z_teacher, queue, Tt)), literally.
+    route="fused": the queue normalised once for both sides, the two cosine GEMMs by torch.matmul without a temperature, softmax,
+    log-softmax, the pointwise KL, its sum and all their backwards in QueueKLDFn's two kernels.  The rows are normalised with autograd and
+    the GEMM's backward carries the cosine gradients on, as on the torch route."""
+    if route not in KLD_ROUTES:
+        raise ValueError(f"queue_kld: route is 'torch' or 'fused', got {route!r}")
+    if route == "torch":
+        from .pretrain_2D import KLD
+        return KLD()(compute_logits(z_student, queue, Ts), compute_logits(z_teacher, queue, Tt))
+    qn_t = nn.functional.normalize(queue, dim=1).T
+    cs = torch.matmul(nn.functional.normalize(z_student, dim=1), qn_t)
+    ct = torch.matmul(nn.functional.normalize(z_teacher, dim=1), qn_t)
+    return QueueKLDFn.apply(cs, ct, float(Ts), float(Tt))
+
+
+def isd_embeddings(isd, im_q, im_k):
+    """The training-mode forward up to the embeddings, before any logits: (outputs, ema_output_tmp, lat_q, lat_k, stu, tea, tea_tmp, queue,
+    queue_mask) - the student's and the first teacher pass's segmentation outputs, the latent rows [B, F] of student and teacher, the
+    patch-wise output rows [n, P] of both, the teacher's rows in the layout the mask queue stores, and the snapshots of the two queues,
+    taken before the enqueue.  The reshapes are the reference's, view for view (they interleave patch and batch indices; the queues are
+    stored in the layout they produce).  The KEY heads are not under no_grad in the reference (:268,282): they are EMA-updated and, being
+    part of the KLD targets' graph, trained by the optimizer too."""
     batch_size = im_q.shape[0]
-    if not isd.training:
-        outputs, latent_vector, _ = isd.model(im_q)
-        return outputs, latent_vector
     outputs, latent_vector, _ = isd.model(im_q)
     with torch.no_grad():
         ema_output_tmp, _, _ = isd.ema_model(im_k)
@@ -272,11 +333,43 @@ def isd_forward(isd, im_q, im_k=None, Ts=None, Tt=None):
     stu = stu.reshape(-1, stu.shape[0]).contiguous()
     tea = tea.reshape(-1, tea.shape[0]).contiguous()
     queue_mask = queue_mask.reshape(-1, queue_mask.shape[0]).contiguous()
+    return outputs, ema_output_tmp, lat_q, lat_k, stu, tea, tea_tmp, queue, queue_mask
+
+
+def isd_enqueue(isd, lat_k, tea_tmp):
+    with torch.no_grad():
+        dequeue_and_enqueue(isd.K, lat_k, isd.queue, isd.queue_ptr)
+        dequeue_and_enqueue(isd.K, tea_tmp, isd.queue_mask, isd.mask_queue_ptr)
+
+
+def isd_forward(isd, im_q, im_k=None, Ts=None, Tt=None):
+    """Returns (outputs, ema_output, ema_latent_logits, latent_logits, ema_output_logits, output_logits) in training mode,
+    (outputs, latent) in eval mode; see isd_embeddings.  The logits are true logits whatever isd.kld says: the steppers take that route
+    through isd_kld_terms, which builds none."""
+    Ts = Ts if Ts else isd.Ts
+    Tt = Tt if Tt else isd.Tt
+    if not isd.training:
+        outputs, latent_vector, _ = isd.model(im_q)
+        return outputs, latent_vector
+    outputs, ema_output_tmp, lat_q, lat_k, stu, tea, tea_tmp, queue, queue_mask = isd_embeddings(isd, im_q, im_k)
     ema_latent_logits = compute_logits(lat_k, queue, Tt)
     latent_logits = compute_logits(lat_q, queue, Ts)
     ema_output_logits = compute_logits(tea, queue_mask, Tt)
     output_logits = compute_logits(stu, queue_mask, Ts)
-    with torch.no_grad():
-        dequeue_and_enqueue(isd.K, lat_k, isd.queue, isd.queue_ptr)
-        dequeue_and_enqueue(isd.K, tea_tmp, isd.queue_mask, isd.mask_queue_ptr)
+    isd_enqueue(isd, lat_k, tea_tmp)
     return outputs, ema_output_tmp, ema_latent_logits, latent_logits, ema_output_logits, output_logits
+
+
+def isd_kld_terms(isd, im_q, im_k, Ts=None, Tt=None):
+    """The training-mode forward for a stepper on a kld route that builds no logits: (outputs, ema_output, loss_latent, loss_output) with
+    the two terms from queue_kld(route=isd.kld).  Generator consumption, queue snapshots and the enqueue are isd_forward's."""
+    route = getattr(isd, "kld", "torch")
+    if route not in KLD_ROUTES:
+        raise ValueError(f"kld is 'torch' or 'fused', got {route!r}")
+    Ts = Ts if Ts else isd.Ts
+    Tt = Tt if Tt else isd.Tt
+    outputs, ema_output_tmp, lat_q, lat_k, stu, tea, tea_tmp, queue, queue_mask = isd_embeddings(isd, im_q, im_k)
+    loss_latent = queue_kld(lat_q, lat_k, queue, Ts, Tt, route)
+    loss_output = queue_kld(stu, tea, queue_mask, Ts, Tt, route)
+    isd_enqueue(isd, lat_k, tea_tmp)
+    return outputs, ema_output_tmp, loss_latent, loss_output

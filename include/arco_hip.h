@@ -785,6 +785,26 @@ int arco_patch_head_wgrad_finish(const double* ws, int nd, int B, int C, int n0,
                                  int c1, int c2, int c3, int c4, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3,
                                  float* gw4, float* gb4, void* stream);
 
+/* The KL-divergence-to-queue loss of stage 1 as two kernels (pretrain_2D / pretrain_3D --kld fused; csrc/queue_kld.hip, arco_amd/stage1.py
+ * QueueKLDFn): loss = F.kl_div(F.log_softmax(cs / Ts, 1), F.softmax(ct / Tt, 1), 'batchmean') of two row-major fp32 matrices of raw cosines
+ * cs, ct [N, L] with row strides ld_s, ld_t >= L (in floats) and the inverse temperatures inv_ts = 1 / Ts, inv_tt = 1 / Tt, both > 0 and finite.
+ * fwd: one pass over each matrix (online softmax with the true running row maxima).  stats [N, 3] float64 = per row lse_s, lse_t and
+ *   KL_i = sum_j p_ij ((t_ij - lse_t) - (s_ij - lse_s)), s = cs * inv_ts, t = ct * inv_tt, p = softmax(t); a term with p_ij = 0 adds 0.
+ *   loss [1] fp32 = (sum of KL_i in float64, in a fixed order) / N, from a second small launch.  A non-finite cosine makes the loss non-finite.
+ * bwd: g [1] fp32 on the device, the gradient of the loss.  dcs_ij = g (softmax(s)_ij - p_ij) inv_ts / N with row stride ld_ds,
+ *   dct_ij = g p_ij ((t_ij - lse_t) - (s_ij - lse_s) - KL_i) inv_tt / N with row stride ld_dt; a null dcs or dct: not wanted (not both).
+ *   dcs may be cs and dct may be ct (then with that matrix's stride): the gradient replaces the cosines.  Any other overlap of the four
+ *   matrices is the caller's error; dcs == ct, dct == cs and dcs == dct are refused.
+ * Rows of up to arco_queue_kld_short_max() elements take one wave each, longer rows one workgroup of 256 threads each; 16-byte accesses
+ * where L, every stride and every pointer allow them, scalar ones otherwise.  No atomics: two runs give the same bits.
+ * ARCO_ERR_ARG before any launch for a null pointer, N or L outside 1 .. 2^31 - 1, a stride below L or above 2^31 - 1, or a temperature
+ * factor that is not positive and finite. */
+long arco_queue_kld_short_max(void);
+int arco_queue_kld_fwd(const float* cs, const float* ct, long N, long L, long ld_s, long ld_t, float inv_ts, float inv_tt, double* stats,
+                       float* loss, void* stream);
+int arco_queue_kld_bwd(const float* cs, const float* ct, long N, long L, long ld_s, long ld_t, float inv_ts, float inv_tt, const double* stats,
+                       const float* g, float* dcs, long ld_ds, float* dct, long ld_dt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
